@@ -9,9 +9,12 @@ with the depth maps of the previous round exchanged between ranks at the two rou
 collectives besides the initial image broadcast).  `--with-filter` appends the cross-view filter of config 5 to the step (all-gather of
 depth + confidence, FilterDepthMap on the rank's own views, SceneDensify.cpp:2136-2222).  Inputs are resident in HBM before the clock starts.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]        (N > 1: under torch.distributed.run)
 
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries (outside the timed region):
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (`roofline` is formed from the timed steps' own
+statistics and the committed counter file; no run of its own).  `--dump-outputs DIR` writes a fixed sample of the last timed step's maps first.
+With `--full`, at N = 1 the line also carries (outside the timed region; each leg can be left out with its --no-* flag):
+  shard_rates, scaling_model, tiled_sweeps -- the blocks one rank owns at 2 / 4 / 8 GPUs and the opt-in tiled sweeps, timed on this GPU;
   config2  -- BASELINE config 2 through the one-call boundary (pmhip_estimate_depth_map, host buffers in / out): seconds per depth map;
   parity   -- the 9-view 1920x1080 scene against the committed digests of the sequential CPU oracle (tests/golden/), all 27 maps,
               plus a small live oracle-vs-engine comparison;
@@ -66,7 +69,12 @@ def parse():
     ap.add_argument("--wide8-pixels", type=int, default=0, help="PMHipTuning::wide8Pixels (0 = the engine's default)")
     ap.add_argument("--tiles", type=int, default=0, help="OPT-IN estimator mode, not the reference's sweep: tiled sweeps with tiles of this many pixels (pmhip_set_sweep_tiles); the line says so")
     ap.add_argument("--no-tiled-leg", action="store_true", help="skip the tiled-sweeps leg (the opt-in mode's rates at the full batch and at the shard sizes)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, run the extra legs too (shard rates, tiled sweeps, config2 / parity, sgm, cpu baseline; 1 GPU only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's depth / normal / confidence maps as DIR/<name>.npy (float32)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def main():
@@ -253,6 +261,14 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     mpix = V * W * H * a.steps / dt / 1e6
+    if a.dump_outputs:
+        def gather(own):
+            if dist_on:
+                box = [None] * world
+                dist.all_gather_object(box, own)
+                own = {k: v for d in box for k, v in d.items()}
+            return own
+        dump_outputs(a.dump_outputs, eng, mine, slot, V, W, H, gather, write=rank == 0)
     digests = None
     if os.environ.get("OPENMVS_AMD_BENCH_DIGESTS") == "1":   # sha-1 of every view's final depth map, gathered: equal between a 1-rank and an N-rank run of the same scene
         import hashlib
@@ -319,12 +335,13 @@ def main():
                                  "valu_* = SURVEY 8(d)'s 0.33 MFLOP per output pixel x this GPU's pixel rate against the FP32 vector peak"},
             "accuracy": {"valid_frac_view0": round(float(m.mean()), 4), "median_rel_err_vs_ground_truth": float(np.median(rel))},
         }
-    # ---- extra legs (rank 0, 1 GPU only; outside the timed region) ---------------------------
-    if rank == 0 and world == 1 and not weak and not a.no_shard_rates and V >= 16:
+    # ---- extra legs (--full; rank 0, 1 GPU only; outside the timed region) ---------------------------
+    extras = a.full and rank == 0 and world == 1
+    if extras and not weak and not a.no_shard_rates and V >= 16:
         out.update(shard_rate_legs(eng, a, V, W, H, p, mpix))
-    if rank == 0 and world == 1 and not weak and not a.no_tiled_leg and not a.tiles and V >= 16:
+    if extras and not weak and not a.no_tiled_leg and not a.tiles and V >= 16:
         out.update(tiled_legs(eng, a, V, W, H, p, mpix))
-    if rank == 0 and world == 1:
+    if extras:
         eng.scene_create(2, 16, 16, 0)   # release the benchmark scene's HBM before the other legs
         if not a.no_extras:
             out.update(golden_and_config2(eng))
@@ -336,6 +353,27 @@ def main():
     eng.close()
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 48 << 20        # --dump-outputs writes at most this much; the whole maps of the default scene are 4 GB
+
+
+def dump_outputs(path, eng, mine, slot, V, W, H, gather, write):
+    """What the timed path returns to its caller -- depth, normal and confidence map of every reference view, as pmhip_scene_get_maps gives them after the last
+    timed step -- at a fixed, seeded sample of pixel positions, the same positions in every view: DIR/depth.npy (views, pixels), DIR/normal.npy (views, pixels, 3),
+    DIR/confidence.npy (views, pixels), float32, views in scene order.  The sample depends on (views, width, height) only."""
+    n_px = max(1, min(W * H, DUMP_BYTES // (4 * 5 * V)))
+    pick = np.sort(np.random.RandomState(20240607).choice(W * H, n_px, replace=False))
+    own = {}
+    for g in mine:
+        d, n, c = eng.scene_get_maps(slot[g])
+        own[g] = (d.reshape(-1)[pick], n.reshape(-1, 3)[pick], c.reshape(-1)[pick])
+    own = gather(own)
+    if write:
+        os.makedirs(path, exist_ok=True)
+        views = sorted(own)
+        for i, name in enumerate(("depth", "normal", "confidence")):
+            np.save(os.path.join(path, name + ".npy"), np.stack([own[g][i] for g in views]).astype(np.float32))
 
 
 def shard_rate_legs(eng, a, V, W, H, p, rate_full):

@@ -1,5 +1,6 @@
 """Writes tests/golden/depth0007.dmap with OUR writer and checks it with the REFERENCE's own reader
-(scripts/python/MvsUtils.py:9-70, importable only in the build container).  Run from the repo root."""
+(scripts/python/MvsUtils.py:9-70, importable only where the reference tree is); what that reader returned for the file is kept as
+tests/golden/depth0007_loaddmap.npz, which tests/test_dmap.py checks without the reference.  Run from the repo root."""
 import os
 import sys
 
@@ -34,4 +35,5 @@ if __name__ == "__main__":
     assert np.array_equal(d["depth_map"], c["depth"]) and np.array_equal(d["normal_map"], c["normal"]) and np.array_equal(d["confidence_map"], c["conf"])
     assert np.array_equal(d["views_map"], c["views"]) and np.array_equal(d["K"], c["K"]) and np.array_equal(d["R"], c["R"]) and np.array_equal(d["C"], c["Cc"])
     assert abs(d["depth_min"] - 0.25) < 1e-7 and abs(d["depth_max"] - 7.5) < 1e-7
+    np.savez_compressed(os.path.join(HERE, "depth0007_loaddmap.npz"), **{k: d[k] for k in ("depth_map", "normal_map", "views_map")})
     print("reference reader parsed our file identically:", path, os.path.getsize(path), "bytes")

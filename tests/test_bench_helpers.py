@@ -53,3 +53,33 @@ def test_roofline_fields_from_the_counter_file():
     assert 0.5 < g["frac"] < 1.05 and 400 <= g["wave_loads_per_wave_visit"] < 520 and abs(g["peak"] - 256 * 2.4 / 64.5) < 0.01
     assert b.sweep_kernel_name(100, 8) == "pm_sweep2_kernel" and b.sweep_kernel_name(13, 8).startswith("pm_sweep_widen_kernel") and b.sweep_kernel_name(1, 8) == "pm_sweep_wide_kernel"
     assert b.usable_cores() >= 1
+
+
+def test_dump_outputs_is_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: the maps of every view at the same seeded pixel positions, float32, views in scene order; a small scene is written whole, and the
+    benchmark's default scene (100 views of 1920x1080) stays within 64 MB with the same sample from run to run."""
+    import numpy as np
+    b = _bench()
+    r = np.random.RandomState(0)
+    small = {g: (r.rand(30, 40).astype(np.float32), r.rand(30, 40, 3).astype(np.float32), r.rand(30, 40).astype(np.float32)) for g in range(3)}
+
+    class Engine:
+        def __init__(self, maps):
+            self.maps = maps
+
+        def scene_get_maps(self, i):
+            return self.maps(i)
+    b.dump_outputs(str(tmp_path / "small"), Engine(small.get), [2, 0, 1], {g: g for g in range(3)}, 3, 40, 30, lambda own: own, True)
+    for i, name in enumerate(("depth", "normal", "confidence")):
+        got = np.load(tmp_path / "small" / (name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, np.stack([small[g][i].reshape(30 * 40, -1).squeeze() for g in range(3)]))
+    W, H, V = 1920, 1080, 100
+    index = (np.arange(W * H, dtype=np.float32).reshape(H, W), np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32))     # depth = the pixel's index
+    picks = []
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), Engine(lambda i: index), list(range(V)), {g: g for g in range(V)}, V, W, H, lambda own: own, True)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 64e6
+        d = np.load(tmp_path / run / "depth.npy")
+        assert d.shape[0] == V and d.shape[1] > 10000 and (d == d[0]).all() and (np.diff(d[0]) > 0).all()
+        picks.append(d[0])
+    assert np.array_equal(picks[0], picks[1])

@@ -1,6 +1,7 @@
 """The reference's dense option table and the two text files in front of the path (`--dense-config-file`, `--view-neighbors-file`): include/optdense.h,
 mvsf_load_view_neighbors / mvsf_save_view_neighbors (libmvsfront.so) and their numpy mirrors (openmvs_amd/optdense.py, mvsi.py, views.py)."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -11,7 +12,7 @@ from openmvs_amd import mvsfront, mvsi, optdense, views
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SCENE = os.path.join(HERE, "data", "scene", "scene.mvs")
-REF_DEPTHMAP = "/root/reference/libs/MVS/DepthMap.cpp"
+OPTDENSE_TABLE = os.path.join(HERE, "golden", "optdense_table.json")
 
 
 def test_abi_exports_every_declared_symbol():
@@ -22,14 +23,10 @@ def test_abi_exports_every_declared_symbol():
 
 
 @pytest.mark.pinning
-@pytest.mark.skipif(not os.path.exists(REF_DEPTHMAP), reason="needs /root/reference")
 def test_table_is_the_reference_option_list():
-    """Variable, title, type and first default of every DEFVAR_OPTDENSE_* / MDEFVAR_OPTDENSE_* line of libs/MVS/DepthMap.cpp, in order."""
-    ref = []
-    for line in open(REF_DEPTHMAP, encoding="utf-8", errors="replace"):
-        m = re.match(r'M?DEFVAR_OPTDENSE_(\w+)\((\w+), "([^"]*)", "[^"]*", "([^"]*)"', line)
-        if m:
-            ref.append((m.group(2), m.group(3), m.group(1), m.group(4)))
+    """Variable, title, type and first default of every DEFVAR_OPTDENSE_* / MDEFVAR_OPTDENSE_* line of libs/MVS/DepthMap.cpp, in order (tests/golden/optdense_table.json,
+    extracted from the reference by tests/golden/make_optdense_golden.py)."""
+    ref = [tuple(r) for r in json.load(open(OPTDENSE_TABLE))]
     assert len(ref) == 46
     assert optdense.table() == ref
 

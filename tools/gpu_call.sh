@@ -27,10 +27,10 @@ suite)
   echo "exit $?" >> "$OUT/gpu_suite.log"; tail -15 "$OUT/gpu_suite.log" ;;
 bench)
   step "bench"
-  timeout 900 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "rc $?"; tail -c 1500 "$OUT/bench.json"; tail -3 "$OUT/bench.err" ;;
+  timeout 900 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "rc $?"; tail -c 1500 "$OUT/bench.json"; tail -3 "$OUT/bench.err" ;;
 prof)
   step "rocprof kernel stats of bench.py"
-  ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o bench -- python "$R/bench.py" --no-cpu-baseline ${BENCH_ARGS:-} \
+  ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o bench -- python "$R/bench.py" --full --no-cpu-baseline ${BENCH_ARGS:-} \
       > "$R/$OUT/bench_under_rocprof.json" 2> "$R/$OUT/rocprof.err" ); echo "rc $?"
   find /tmp/prof_stats -name "*kernel_stats.csv" -exec cp {} "$OUT/bench_kernel_stats.csv" \; ; rm -rf /tmp/prof_stats
   head -8 "$OUT/bench_kernel_stats.csv"; tail -c 400 "$OUT/bench_under_rocprof.json" ;;
