@@ -38,6 +38,10 @@ public:
 		float fDepthDiffThreshold = 0.01f, fNormalDiffThreshold = 25.f;
 		unsigned nMinViewsFilter = 2, nMinViewsFilterAdjust = 1, nMinViewsFuse = 2;
 		bool bFilterAdjust = true, bEstimateColor = true, bEstimateNormal = true;
+		// the finishing steps after the fusion (FinishPointCloud, SceneDensify.cpp:1733-1736): EstimatePointColors / EstimatePointNormals when the cloud has
+		// none -- OPTDENSE::nEstimateColors == 1 / nEstimateNormals == 1; nNeighbors = the k of the PCA normals
+		bool bPointColors = false, bPointNormals = false;
+		int nNeighbors = 16;
 		Options() { pmhip_default_params(this); }
 	};
 
@@ -152,6 +156,34 @@ public:
 		pc.colors.assign(haveColor ? (size_t)nP * 3 : 0, (unsigned char)0); pc.normals.assign(opt.bEstimateNormal ? (size_t)nP * 3 : 0, 0.f);
 		chk(pmhip_scene_fuse_get(e, pc.points.data(), pc.viewStart.data(), pc.views.data(), pc.weights.data(), pc.projs.data(),
 		                         haveColor ? pc.colors.data() : nullptr, opt.bEstimateNormal ? pc.normals.data() : nullptr));
+	}
+
+	// TOBB<float,3> after Set(rot, ptMin, ptMax) (Scene::obb): row-major rotation, centre, half-extents
+	struct OBB { float rot[9], pos[3], ext[3]; };
+	// The block after the fusion (SceneDensify.cpp:1724-1737) on the cloud FuseDepthMaps left on the device: RemovePointsOutside(ROI) when bCrop2ROI (the caller
+	// tests Scene::IsBounded; fBorderROI > 0 enlarges the extents by that factor, < 0 adds -fBorderROI), then EstimatePointColors / EstimatePointNormals as
+	// Options::bPointColors / bPointNormals ask and `pc` has none.  `pc` is replaced by the finished cloud.
+	void FinishPointCloud(PointCloud& pc, const OBB& roi, bool bCrop2ROI, float fBorderROI) { FinishOn(e_, opt_, pc, roi, bCrop2ROI, fBorderROI); }
+	static void FinishOn(pmhip_engine* e, const Options& opt, PointCloud& pc, const OBB& roi, bool bCrop2ROI, float fBorderROI) {
+		auto chk = [e](int rc) { if (rc != PMHIP_OK) throw std::runtime_error(std::string("pmhip: ") + pmhip_last_error(e)); };
+		if (pc.size() == 0) return;                                                       // if (!pointcloud.IsEmpty())
+		PMHipCloudParams p;
+		memset(&p, 0, sizeof(p));
+		p.bCrop = bCrop2ROI ? 1 : 0;
+		memcpy(p.obbRot, roi.rot, sizeof(p.obbRot)); memcpy(p.obbPos, roi.pos, sizeof(p.obbPos)); memcpy(p.obbExt, roi.ext, sizeof(p.obbExt));
+		p.fBorderROI = fBorderROI;
+		p.bEstimateColor = opt.bPointColors && pc.colors.empty() ? 1 : 0;
+		p.bEstimateNormal = opt.bPointNormals && pc.normals.empty() ? 1 : 0;
+		p.nNeighbors = opt.nNeighbors;
+		if (!p.bCrop && !p.bEstimateColor && !p.bEstimateNormal) return;
+		const bool color = !pc.colors.empty() || p.bEstimateColor, normal = !pc.normals.empty() || p.bEstimateNormal;
+		uint64_t nP = 0, nV = 0;
+		chk(pmhip_scene_cloud_finish(e, &p, &nP, &nV));
+		pc.points.assign((size_t)nP * 3, 0.f); pc.viewStart.assign((size_t)nP + 1, 0u); pc.views.assign((size_t)nV, 0u); pc.weights.assign((size_t)nV, 0.f);
+		pc.projs.assign((size_t)nV * 2, (uint16_t)0);
+		pc.colors.assign(color ? (size_t)nP * 3 : 0, (unsigned char)0); pc.normals.assign(normal ? (size_t)nP * 3 : 0, 0.f);
+		chk(pmhip_scene_fuse_get(e, pc.points.data(), pc.viewStart.data(), pc.views.data(), pc.weights.data(), pc.projs.data(),
+		                         color ? pc.colors.data() : nullptr, normal ? pc.normals.data() : nullptr));
 	}
 
 	// One view's maps back to the host (any pointer may be null); ViewWidth(idx) x ViewHeight(idx) entries

@@ -170,6 +170,10 @@ public:
 		for (int d = 0; d < NumDevices(); ++d) check(d, pmhip_sync(eng_[(size_t)d]));
 		DenseDepthMapsHIP::FuseOn(eng_[0], views_, opt_, pc);
 	}
+	// the block after the fusion (crop to the ROI, colours, PCA normals) on the fusing device, where the cloud lies: see DenseDepthMapsHIP::FinishPointCloud
+	void FinishPointCloud(PointCloud& pc, const DenseDepthMapsHIP::OBB& roi, bool bCrop2ROI, float fBorderROI) {
+		DenseDepthMapsHIP::FinishOn(eng_[0], opt_, pc, roi, bCrop2ROI, fBorderROI);
+	}
 	// a view's maps from the device that owns it; ViewWidth(idx) x ViewHeight(idx) entries
 	int ViewWidth(int idx) const { return sized(idx) ? views_[(size_t)idx].w : w_; }
 	int ViewHeight(int idx) const { return sized(idx) ? views_[(size_t)idx].h : h_; }

@@ -22,6 +22,8 @@ inline DenseDepthMapsHIP::Options DenseOptionsFrom(const MVSFOptDense& o, uint32
 	d.bFilterAdjust = o.bFilterAdjust != 0;
 	d.bEstimateColor = o.nEstimateColors == 2;             // FuseDepthMaps(pointcloud, nEstimateColors == 2, nEstimateNormals == 2), SceneDensify.cpp:1697-1700
 	d.bEstimateNormal = o.nEstimateNormals == 2;
+	d.bPointColors = o.nEstimateColors == 1;              // EstimatePointColors / EstimatePointNormals after it (:1733-1736): FinishPointCloud
+	d.bPointNormals = o.nEstimateNormals == 1;
 	return d;
 }
 

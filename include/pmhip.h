@@ -201,6 +201,29 @@ int pmhip_scene_fuse_get(pmhip_engine* e, float* points, uint32_t* viewStart, ui
                          unsigned char* colors, float* normals);
 /* Reservation rounds the last pmhip_scene_fuse needed, summed over its views (diagnostic). */
 uint64_t pmhip_scene_fuse_rounds(pmhip_engine* e);
+/* The last block of Scene::DenseReconstruction on the resident cloud (SceneDensify.cpp:1724-1737), in the reference's order: crop to the ROI
+ * (PointCloud::RemovePointsOutside, the backward swap-remove order of PointCloud.cpp:82-87 reproduced exactly for points, views, weights,
+ * projections, colours and normals), colours (EstimatePointColors, DepthMap.cpp:1429-1465, bit-exact; needs pmhip_scene_set_color for every
+ * view a point lists) when the cloud has none, and PCA normals over the nNeighbors nearest points (EstimatePointNormals, DepthMap.cpp:1469-1519;
+ * the point itself is one of them, distance ties go to the lower index) when it has none.  Works on the cloud of the last pmhip_scene_fuse or
+ * pmhip_scene_cloud_set; pmhip_scene_fuse_get returns the result.  nPoints / nViews: the sizes after the crop (either may be NULL). */
+typedef struct PMHipCloudParams {
+	int32_t bCrop;                           /* RemovePointsOutside(ROI); the caller tests Scene::IsBounded */
+	float obbRot[9], obbPos[3], obbExt[3];   /* TOBB<float,3> after Set(rot, ptMin, ptMax): row-major rotation, centre, half-extents */
+	float fBorderROI;                        /* > 0: extents multiplied (EnlargePercent), < 0: -fBorderROI added (Enlarge), 0: as is (SceneDensify.cpp:1728) */
+	int32_t bEstimateColor;                  /* EstimatePointColors, if the cloud has no colours */
+	int32_t bEstimateNormal;                 /* EstimatePointNormals, if the cloud has no normals */
+	int32_t nNeighbors;                      /* k of the PCA (16), 1..32 */
+} PMHipCloudParams;
+int pmhip_scene_cloud_finish(pmhip_engine* e, const PMHipCloudParams* p, uint64_t* nPoints, uint64_t* nViews);
+/* Replace the resident cloud with a host cloud (an archive's points, a test cloud): points 3*nPoints floats, viewStart nPoints+1 offsets,
+ * views (image indices of the loaded scene, at least one per point), weights (may be NULL: zeros).  The cloud has no colours, normals or projections. */
+int pmhip_scene_cloud_set(pmhip_engine* e, const float* points, const uint32_t* viewStart, const uint32_t* views, const float* weights, uint64_t nPoints);
+/* Diagnostic, also what the tests check: the nNeighbors (1..32) indices of each listed query point, nearest first, as the normals use them
+ * (out: nQueries*nNeighbors; entries beyond the cloud's size are 0xFFFFFFFF). */
+int pmhip_scene_cloud_knn(pmhip_engine* e, int nNeighbors, const uint32_t* queries, uint32_t nQueries, uint32_t* out);
+/* Milliseconds of the steps of the last pmhip_scene_cloud_finish, each ended by a stream synchronisation: crop, grid build, k-NN + PCA, colours. */
+int pmhip_scene_cloud_times(pmhip_engine* e, double ms[4]);
 /* Device-to-device copy between a caller buffer (e.g. a torch tensor used for an RCCL collective)
  * and `count` consecutive views of one per-kind array, starting at view firstIdx; `what` as above.
  * toEngine != 0 copies caller -> engine.  Asynchronous on the engine stream. */
@@ -250,8 +273,8 @@ typedef struct PMHipTuning {
  * that it differs like two runs of the reference differ from each other.  0, 0 = off (the default: the reference's sweep, bit for bit). */
 int pmhip_set_sweep_tiles(pmhip_engine* e, int tileW, int tileH);
 /* The layout of the structs of this header as a number: a host program compares pmhip_abi_version() with the PMHIP_ABI_VERSION it was compiled against before it hands the
- * library a struct (6: PMHipTuning is 32 bytes again -- reserved0; pmhip_set_sweep_tiles). */
-#define PMHIP_ABI_VERSION 6u
+ * library a struct (6: PMHipTuning is 32 bytes again -- reserved0; pmhip_set_sweep_tiles; 7: PMHipCloudParams). */
+#define PMHIP_ABI_VERSION 7u
 uint32_t pmhip_abi_version(void);
 int pmhip_get_tuning(pmhip_engine* e, PMHipTuning* out);
 int pmhip_set_tuning(pmhip_engine* e, const PMHipTuning* t);

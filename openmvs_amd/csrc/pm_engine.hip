@@ -10,6 +10,7 @@
 #include "pm_wide_n.hip"
 #include "pm_filter.hip"
 #include "pm_fuse.hip"
+#include "pm_cloud.hip"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -158,6 +159,17 @@ struct pmhip_engine {
 		// scenes whose views differ in size: every image's normal / confidence / colour gathered into [nImages][slab] arrays, and the sizes
 		float *normalS = nullptr, *confS = nullptr; uint8_t* bgrS = nullptr; int* dims = nullptr;
 	} fu;
+	// the finishing steps on the fused cloud (pm_cloud.hip): grow-only working buffers, freed with the scene
+	struct Cloud {
+		PMFuseOut alt{}; size_t altCap = 0;                      // the crop's target, swapped with fu.out afterwards
+		uint8_t* hole = nullptr; uint32_t* nxt = nullptr; uint32_t* cellOf = nullptr; float4* spts = nullptr; size_t ptCap = 0;
+		uint2 *tileSums = nullptr, *tileOff = nullptr; size_t tileCap = 0;
+		uint32_t *counts = nullptr, *cellStart = nullptr; size_t cellCap = 0;
+		PMFuseCam* cams = nullptr; PMClImg* imgs = nullptr; uint32_t* used = nullptr; int imgCap = 0;
+		uint32_t *qbuf = nullptr, *obuf = nullptr; size_t qCap = 0;
+		uint32_t* misc = nullptr; float* sample = nullptr;       // misc: scan totals [0..3], jump flag [4], bounding box [8..13]
+		double ms[4] = {0, 0, 0, 0};
+	} cl;
 	// batch scratch (grow only)
 	int batchCap = 0;
 	float* d_lvl[4] = {nullptr, nullptr, nullptr, nullptr}; // level l>=1: [batch][6][h_l*w_l]; level 0: prior [batch][h*w]
@@ -203,9 +215,18 @@ static void freeFuse(pmhip_engine* e) {
 	f = pmhip_engine::Fuse{};
 }
 
+static void freeCloud(pmhip_engine* e) {
+	auto& c = e->cl;
+	void* ptrs[] = {c.alt.points, c.alt.viewStart, c.alt.views, c.alt.weights, c.alt.projs, c.alt.colors, c.alt.normals, c.hole, c.nxt, c.cellOf, c.spts,
+	                c.tileSums, c.tileOff, c.counts, c.cellStart, c.cams, c.imgs, c.used, c.qbuf, c.obuf, c.misc, c.sample};
+	for (void* q : ptrs) if (q) hipFree(q);
+	c = pmhip_engine::Cloud{};
+}
+
 static void freeScene(pmhip_engine* e) {
 	hipSetDevice(e->device);
 	freeFuse(e);
+	freeCloud(e);
 	for (int l = 0; l < 4; ++l) { if (e->d_img[l]) hipFree(e->d_img[l]); e->d_img[l] = nullptr; if (e->d_imgS[l]) hipFree(e->d_imgS[l]); e->d_imgS[l] = nullptr; if (e->d_imgQ[l]) hipFree(e->d_imgQ[l]); e->d_imgQ[l] = nullptr; if (e->d_lvl[l]) hipFree(e->d_lvl[l]); e->d_lvl[l] = nullptr; if (e->d_old[l]) hipFree(e->d_old[l]); e->d_old[l] = nullptr; }
 	e->oldCap = 0;
 	if (e->d_depth) hipFree(e->d_depth); if (e->d_normal) hipFree(e->d_normal); if (e->d_conf) hipFree(e->d_conf); if (e->d_snap) hipFree(e->d_snap);
@@ -1649,5 +1670,289 @@ int pmhip_scene_fuse_get(pmhip_engine* e, float* points, uint32_t* viewStart, ui
 }
 
 uint64_t pmhip_scene_fuse_rounds(pmhip_engine* e) { return e ? e->fu.rounds : 0; }
+
+
+// ---- the finishing steps on the fused cloud (pm_cloud.hip; SceneDensify.cpp:1724-1737) --------------------------------------------
+#define CLALLOC(e, ptr, n) do { if (ptr) hipFree(ptr); ptr = nullptr; HIPCHK(e, hipMalloc(&(ptr), (n))); } while (0)
+
+static int ensureCloudPoints(pmhip_engine* e, size_t n) {
+	auto& c = e->cl;
+	if (!c.misc) { HIPCHK(e, hipMalloc(&c.misc, sizeof(uint32_t) * 16)); HIPCHK(e, hipMalloc(&c.sample, sizeof(float) * 3 * 1024)); }
+	if (c.ptCap < n + 1) {
+		const size_t cap = n + 1;
+		CLALLOC(e, c.hole, cap); CLALLOC(e, c.nxt, sizeof(uint32_t) * cap); CLALLOC(e, c.cellOf, sizeof(uint32_t) * cap); CLALLOC(e, c.spts, sizeof(float4) * cap);
+		c.ptCap = cap;
+	}
+	const size_t nT = (std::max(n, (size_t)e->cl.cellCap) + PMCL_TILE - 1) / PMCL_TILE + 1;
+	if (c.tileCap < nT) { CLALLOC(e, c.tileSums, sizeof(uint2) * nT); CLALLOC(e, c.tileOff, sizeof(uint2) * nT); c.tileCap = nT; }
+	return 0;
+}
+
+// cameras (P composed like Camera::ComposeP) and the colour image of every view
+static int uploadCloudViews(pmhip_engine* e) {
+	auto& c = e->cl; auto& f = e->fu;
+	const int N = e->nImages;
+	if (c.imgCap < N) { CLALLOC(e, c.cams, sizeof(PMFuseCam) * N); CLALLOC(e, c.imgs, sizeof(PMClImg) * N); CLALLOC(e, c.used, sizeof(uint32_t) * (N + 1)); c.imgCap = N; }
+	std::vector<PMFuseCam> hc((size_t)N); std::vector<PMClImg> hi((size_t)N);
+	const size_t P0 = (size_t)e->w * e->h;
+	for (int i = 0; i < N; ++i) {
+		memset(&hc[i], 0, sizeof(PMFuseCam)); hi[i] = PMClImg{nullptr, e->vw(i), e->vh(i)};
+		if (!e->views[i].set) continue;
+		memcpy(hc[i].K, e->views[i].K, 72); memcpy(hc[i].R, e->views[i].R, 72); memcpy(hc[i].C, e->views[i].C, 24); pmfu_composeP(hc[i]);
+		const bool has = !f.hasBgr.empty() && f.hasBgr[i];
+		if (has) hi[i].bgr = e->views[i].sw ? e->views[i].oBgr : (f.bgr ? f.bgr + 3 * P0 * i : nullptr);
+	}
+	HIPCHK(e, hipMemcpyAsync(c.cams, hc.data(), sizeof(PMFuseCam) * N, hipMemcpyHostToDevice, e->stream));
+	HIPCHK(e, hipMemcpyAsync(c.imgs, hi.data(), sizeof(PMClImg) * N, hipMemcpyHostToDevice, e->stream));
+	HIPCHK(e, hipStreamSynchronize(e->stream));                       // hc / hi live on this frame
+	return 0;
+}
+
+static float orderedToFloat(uint32_t u) { const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; memcpy(&f, &b, 4); return f; }
+
+// the grid over the resident cloud, its points counting-sorted by cell.  Cell edge: the k-th neighbour distance of a sample of the cloud (median),
+// scaled to the whole cloud's density as for a surface; no finer than 1/4096 of the largest extent, and no more cells than twice the points (2^26 at most)
+static int buildGrid(pmhip_engine* e, int k, PMClGrid& g) {
+	auto& c = e->cl; auto& f = e->fu;
+	const uint32_t n = (uint32_t)f.nPoints;
+	int rc = ensureCloudPoints(e, n); if (rc) return rc;
+	const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
+	HIPCHK(e, hipMemsetAsync(c.misc + 8, 0xFF, sizeof(uint32_t) * 3, e->stream));
+	HIPCHK(e, hipMemsetAsync(c.misc + 11, 0, sizeof(uint32_t) * 3, e->stream));
+	hipLaunchKernelGGL(pmcl_bbox_kernel, dim3(nb), dim3(256), 0, e->stream, f.out.points, n, c.misc + 8);
+	const uint32_t S = std::min<uint32_t>(n, 1024);
+	hipLaunchKernelGGL(pmcl_sample_kernel, dim3((S + 255) / 256), dim3(256), 0, e->stream, f.out.points, n, S, c.sample);
+	uint32_t bb[6]; std::vector<float> hs((size_t)S * 3);
+	HIPCHK(e, hipMemcpyAsync(bb, c.misc + 8, sizeof(bb), hipMemcpyDeviceToHost, e->stream));
+	HIPCHK(e, hipMemcpyAsync(hs.data(), c.sample, sizeof(float) * 3 * S, hipMemcpyDeviceToHost, e->stream));
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	double lo[3], ext[3], L = 0;
+	for (int a = 0; a < 3; ++a) { lo[a] = (double)orderedToFloat(bb[a]); ext[a] = (double)orderedToFloat(bb[3 + a]) - lo[a]; L = std::max(L, ext[a]); }
+	if (!(L < 1e300)) { e->err = "cloud: points are not finite"; return PMHIP_E_ARG; }
+	double h = L > 0 ? L / 4096. : 1.;
+	const uint32_t j = std::min<uint32_t>((uint32_t)k, S > 1 ? S - 1 : 1);
+	if (S > 1) {
+		std::vector<double> rk(S), d2(S);
+		for (uint32_t a = 0; a < S; ++a) {
+			for (uint32_t b = 0; b < S; ++b) {
+				const double dx = (double)hs[a*3] - hs[b*3], dy = (double)hs[a*3+1] - hs[b*3+1], dz = (double)hs[a*3+2] - hs[b*3+2];
+				d2[b] = dx * dx + dy * dy + dz * dz;
+			}
+			std::nth_element(d2.begin(), d2.begin() + j, d2.end());      // d2[0] is the point itself
+			rk[a] = d2[j];
+		}
+		std::nth_element(rk.begin(), rk.begin() + S / 2, rk.end());
+		const double r = sqrt(rk[S / 2]) * sqrt((double)k * S / ((double)j * n));
+		h = std::max(h, r);
+	}
+	const double maxCells = (double)std::min<size_t>(std::max<size_t>((size_t)2 * n, 4096), (size_t)1 << 26);
+	int dims[3];
+	for (;;) {
+		double cells = 1;
+		for (int a = 0; a < 3; ++a) { dims[a] = (int)std::min(floor(ext[a] / h) + 1., 1e9); cells *= dims[a]; }
+		if (cells <= maxCells) break;
+		h *= 1.25;
+	}
+	const uint32_t nCells = (uint32_t)dims[0] * dims[1] * dims[2];
+	if (c.cellCap < (size_t)nCells + 1) { CLALLOC(e, c.counts, sizeof(uint32_t) * (nCells + 1)); CLALLOC(e, c.cellStart, sizeof(uint32_t) * (nCells + 1)); c.cellCap = nCells + 1; }
+	rc = ensureCloudPoints(e, n); if (rc) return rc;                   // (tiles for the cell scan)
+	g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2]; g.h = h; g.invh = 1. / h; g.nx = dims[0]; g.ny = dims[1]; g.nz = dims[2];
+	g.cellStart = c.cellStart; g.spts = c.spts;
+	HIPCHK(e, hipMemsetAsync(c.counts, 0, sizeof(uint32_t) * nCells, e->stream));
+	HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
+	hipLaunchKernelGGL(pmcl_count_kernel, dim3(nb), dim3(256), 0, e->stream, f.out.points, n, g, c.cellOf, c.counts);
+	const unsigned nT = (nCells + PMCL_TILE - 1) / PMCL_TILE;
+	hipLaunchKernelGGL(pmcl_tile_sums_u32, dim3(nT), dim3(PMCL_TB), 0, e->stream, c.counts, nCells, c.tileSums);
+	hipLaunchKernelGGL(pmfu_scan_tiles, dim3(1), dim3(1024), 0, e->stream, c.tileSums, nT, c.misc, c.tileOff);
+	hipLaunchKernelGGL(pmcl_scan_apply, dim3(nT), dim3(PMCL_TB), 0, e->stream, c.counts, nCells, c.tileOff, c.cellStart);
+	HIPCHK(e, hipMemcpyAsync(c.cellStart + nCells, &n, sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+	hipLaunchKernelGGL(pmcl_scatter_kernel, dim3(nb), dim3(256), 0, e->stream, f.out.points, n, c.cellOf, c.counts, c.spts);
+	HIPCHK(e, hipGetLastError());
+	HIPCHK(e, hipStreamSynchronize(e->stream));                       // (n lives on this frame)
+	return 0;
+}
+
+static int launchKnn(pmhip_engine* e, bool pca, const PMClGrid& g, int k, uint32_t nq, const PMClKnnOut& o) {
+	const dim3 gr((nq + 255) / 256), bl(256);
+	const float* pts = e->fu.out.points;
+	if (k <= 16) { if (pca) hipLaunchKernelGGL((pmcl_knn_kernel<16, true>), gr, bl, 0, e->stream, g, pts, k, nq, o); else hipLaunchKernelGGL((pmcl_knn_kernel<16, false>), gr, bl, 0, e->stream, g, pts, k, nq, o); }
+	else { if (pca) hipLaunchKernelGGL((pmcl_knn_kernel<32, true>), gr, bl, 0, e->stream, g, pts, k, nq, o); else hipLaunchKernelGGL((pmcl_knn_kernel<32, false>), gr, bl, 0, e->stream, g, pts, k, nq, o); }
+	HIPCHK(e, hipGetLastError());
+	return 0;
+}
+
+// PointCloud::RemovePointsOutside on the resident cloud (see pm_cloud.hip for the order)
+static int cropCloud(pmhip_engine* e, const PMClObb& box) {
+	auto& c = e->cl; auto& f = e->fu;
+	const uint32_t n = (uint32_t)f.nPoints;
+	int rc = ensureCloudPoints(e, n); if (rc) return rc;
+	const unsigned nT = (n + PMCL_TILE - 1) / PMCL_TILE;
+	HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
+	hipLaunchKernelGGL(pmcl_crop_flags, dim3(nT), dim3(PMCL_TB), 0, e->stream, f.out.points, n, box, c.hole, c.tileSums);
+	hipLaunchKernelGGL(pmfu_scan_tiles, dim3(1), dim3(1024), 0, e->stream, c.tileSums, nT, c.misc, c.tileOff);
+	hipLaunchKernelGGL(pmcl_crop_next, dim3(nT), dim3(PMCL_TB), 0, e->stream, c.hole, n, c.tileOff, c.misc, c.nxt);
+	uint32_t H = 0;
+	HIPCHK(e, hipMemcpyAsync(&H, c.misc, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	if (H == 0) return 0;
+	const uint32_t m = n - H;
+	const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+	for (int round = 0; round < 64; ++round) {                          // chains only climb: at most log2(n) + 1 rounds
+		uint32_t changed = 0;
+		HIPCHK(e, hipMemsetAsync(c.misc + 4, 0, sizeof(uint32_t), e->stream));
+		hipLaunchKernelGGL(pmcl_jump, dim3(nb), dim3(256), 0, e->stream, c.nxt, n, c.misc + 4);
+		HIPCHK(e, hipMemcpyAsync(&changed, c.misc + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+		HIPCHK(e, hipStreamSynchronize(e->stream));
+		if (!changed) break;
+	}
+	// the target buffers: as large as the current ones, colours / normals as the cloud has them
+	if (c.altCap < f.cap) {
+		void* ptrs[] = {c.alt.points, c.alt.viewStart, c.alt.views, c.alt.weights, c.alt.projs, c.alt.colors, c.alt.normals};
+		for (void* q : ptrs) if (q) hipFree(q);
+		c.alt = PMFuseOut{}; c.altCap = 0;
+		const size_t cap = f.cap;
+		HIPCHK(e, hipMalloc(&c.alt.points, sizeof(float) * 3 * cap)); HIPCHK(e, hipMalloc(&c.alt.viewStart, sizeof(uint32_t) * (cap + 1)));
+		HIPCHK(e, hipMalloc(&c.alt.views, sizeof(uint32_t) * cap)); HIPCHK(e, hipMalloc(&c.alt.weights, sizeof(float) * cap));
+		HIPCHK(e, hipMalloc(&c.alt.projs, sizeof(uint16_t) * 2 * cap));
+		c.altCap = cap;
+	}
+	if (f.haveColor && !c.alt.colors) HIPCHK(e, hipMalloc(&c.alt.colors, 3 * c.altCap));
+	if (f.haveNormal && !c.alt.normals) HIPCHK(e, hipMalloc(&c.alt.normals, sizeof(float) * 3 * c.altCap));
+	PMFuseOut in = f.out, out = c.alt;
+	if (!f.haveColor) { in.colors = nullptr; out.colors = nullptr; }
+	if (!f.haveNormal) { in.normals = nullptr; out.normals = nullptr; }
+	const unsigned mT = (m + PMCL_TILE - 1) / PMCL_TILE;
+	HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
+	if (m) {
+		hipLaunchKernelGGL(pmcl_crop_tile_sums, dim3(mT), dim3(PMCL_TB), 0, e->stream, c.nxt, f.out.viewStart, m, c.tileSums);
+		hipLaunchKernelGGL(pmfu_scan_tiles, dim3(1), dim3(1024), 0, e->stream, c.tileSums, mT, c.misc, c.tileOff);
+		hipLaunchKernelGGL(pmcl_crop_scatter, dim3(mT), dim3(PMCL_TB), 0, e->stream, in, c.nxt, m, c.tileOff, out);
+	}
+	uint32_t nv = 0;
+	HIPCHK(e, hipMemcpyAsync(&nv, c.misc, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	HIPCHK(e, hipMemcpyAsync(out.viewStart + m, &nv, sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+	HIPCHK(e, hipGetLastError());
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	std::swap(f.out, c.alt); std::swap(f.cap, c.altCap);
+	f.nPoints = m; f.nViews = nv;
+	return 0;
+}
+
+int pmhip_scene_cloud_set(pmhip_engine* e, const float* points, const uint32_t* viewStart, const uint32_t* views, const float* weights, uint64_t nPoints) {
+	if (!e || !viewStart || (nPoints && (!points || !views))) return PMHIP_E_ARG;
+	if (e->nImages < 1) { e->err = "cloud_set: no scene"; return PMHIP_E_STATE; }
+	if (nPoints >= 0xFFFFFFFFull || viewStart[0] != 0) { e->err = "cloud_set: bad sizes"; return PMHIP_E_ARG; }
+	const uint64_t nV = viewStart[nPoints];
+	for (uint64_t i = 0; i < nPoints; ++i) if (viewStart[i + 1] <= viewStart[i]) { e->err = "cloud_set: every point needs a view"; return PMHIP_E_ARG; }
+	for (uint64_t v = 0; v < nV; ++v) if (views[v] >= (uint32_t)e->nImages) { e->err = "cloud_set: view index outside the scene"; return PMHIP_E_ARG; }
+	HIPCHK(e, hipSetDevice(e->device));
+	auto& f = e->fu;
+	const size_t cap = (size_t)std::max<uint64_t>(nPoints, nV) + 1;
+	if (f.cap < cap || !f.out.points) {
+		freeFuseOut(e);
+		HIPCHK(e, hipMalloc(&f.out.points, sizeof(float) * 3 * cap)); HIPCHK(e, hipMalloc(&f.out.viewStart, sizeof(uint32_t) * (cap + 1)));
+		HIPCHK(e, hipMalloc(&f.out.views, sizeof(uint32_t) * cap)); HIPCHK(e, hipMalloc(&f.out.weights, sizeof(float) * cap));
+		HIPCHK(e, hipMalloc(&f.out.projs, sizeof(uint16_t) * 2 * cap));
+		f.cap = cap;
+	}
+	if (nPoints) HIPCHK(e, hipMemcpyAsync(f.out.points, points, sizeof(float) * 3 * nPoints, hipMemcpyHostToDevice, e->stream));
+	HIPCHK(e, hipMemcpyAsync(f.out.viewStart, viewStart, sizeof(uint32_t) * (nPoints + 1), hipMemcpyHostToDevice, e->stream));
+	if (nV) {
+		HIPCHK(e, hipMemcpyAsync(f.out.views, views, sizeof(uint32_t) * nV, hipMemcpyHostToDevice, e->stream));
+		if (weights) HIPCHK(e, hipMemcpyAsync(f.out.weights, weights, sizeof(float) * nV, hipMemcpyHostToDevice, e->stream));
+		else HIPCHK(e, hipMemsetAsync(f.out.weights, 0, sizeof(float) * nV, e->stream));
+		HIPCHK(e, hipMemsetAsync(f.out.projs, 0, sizeof(uint16_t) * 2 * nV, e->stream));
+	}
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	f.nPoints = nPoints; f.nViews = nV; f.nDepths = 0; f.rounds = 0; f.haveColor = f.haveNormal = false;
+	return 0;
+}
+
+int pmhip_scene_cloud_knn(pmhip_engine* e, int nNeighbors, const uint32_t* queries, uint32_t nQueries, uint32_t* out) {
+	if (!e || nNeighbors < 1 || nNeighbors > 32 || (nQueries && (!queries || !out))) return PMHIP_E_ARG;
+	auto& f = e->fu; auto& c = e->cl;
+	if (!f.out.points || !f.nPoints) { e->err = "cloud_knn: no cloud"; return PMHIP_E_STATE; }
+	for (uint32_t i = 0; i < nQueries; ++i) if (queries[i] >= f.nPoints) { e->err = "cloud_knn: query outside the cloud"; return PMHIP_E_ARG; }
+	HIPCHK(e, hipSetDevice(e->device));
+	const int k = (int)std::min<uint64_t>((uint64_t)nNeighbors, f.nPoints);
+	PMClGrid g; int rc = buildGrid(e, k, g); if (rc) return rc;
+	if (!nQueries) return 0;
+	if (c.qCap < (size_t)nQueries * k) { CLALLOC(e, c.qbuf, sizeof(uint32_t) * nQueries); CLALLOC(e, c.obuf, sizeof(uint32_t) * (size_t)nQueries * k); c.qCap = (size_t)nQueries * k; }
+	HIPCHK(e, hipMemcpyAsync(c.qbuf, queries, sizeof(uint32_t) * nQueries, hipMemcpyHostToDevice, e->stream));
+	PMClKnnOut o; memset(&o, 0, sizeof(o)); o.queries = c.qbuf; o.idx = c.obuf;
+	rc = launchKnn(e, false, g, k, nQueries, o); if (rc) return rc;
+	std::vector<uint32_t> tmp((size_t)nQueries * k);
+	HIPCHK(e, hipMemcpyAsync(tmp.data(), c.obuf, sizeof(uint32_t) * tmp.size(), hipMemcpyDeviceToHost, e->stream));
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	for (uint32_t q = 0; q < nQueries; ++q)
+		for (int j = 0; j < nNeighbors; ++j) out[(size_t)q * nNeighbors + j] = j < k ? tmp[(size_t)q * k + j] : PMCL_NONE;
+	return 0;
+}
+
+int pmhip_scene_cloud_finish(pmhip_engine* e, const PMHipCloudParams* p, uint64_t* nPoints, uint64_t* nViews) {
+	if (!e || !p) return PMHIP_E_ARG;
+	auto& f = e->fu; auto& c = e->cl;
+	if (!f.out.points) { e->err = "cloud_finish: no cloud (pmhip_scene_fuse or pmhip_scene_cloud_set first)"; return PMHIP_E_STATE; }
+	if (p->bEstimateNormal && (p->nNeighbors < 1 || p->nNeighbors > 32)) { e->err = "cloud_finish: nNeighbors must be 1..32"; return PMHIP_E_ARG; }
+	HIPCHK(e, hipSetDevice(e->device));
+	for (double& t : c.ms) t = 0;
+	using clk = std::chrono::steady_clock;
+	auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+	int rc = 0;
+	if (p->bCrop && f.nPoints) {                                       // (the reference skips the whole block for an empty cloud)
+		const auto t0 = clk::now();
+		PMClObb box; memcpy(box.rot, p->obbRot, sizeof(box.rot)); memcpy(box.pos, p->obbPos, sizeof(box.pos));
+		for (int a = 0; a < 3; ++a) box.ext[a] = p->fBorderROI == 0 ? p->obbExt[a] : p->fBorderROI > 0 ? p->obbExt[a] * p->fBorderROI : p->obbExt[a] + (-p->fBorderROI);
+		rc = cropCloud(e, box); if (rc) return rc;
+		c.ms[0] = ms(t0);
+	}
+	const bool wantColor = p->bEstimateColor && !f.haveColor && f.nPoints, wantNormal = p->bEstimateNormal && !f.haveNormal && f.nPoints;
+	if (wantColor || wantNormal) { rc = uploadCloudViews(e); if (rc) return rc; }
+	const uint32_t n = (uint32_t)f.nPoints;
+	if (wantColor) {
+		const auto t0 = clk::now();
+		// every view a point lists must have its colour image (the reference loads them all; a view without one here is a caller error)
+		const int N = e->nImages;
+		HIPCHK(e, hipMemsetAsync(c.used, 0, sizeof(uint32_t) * (N + 1), e->stream));
+		hipLaunchKernelGGL(pmcl_mark_views, dim3((unsigned)std::min<uint64_t>((f.nViews + 255) / 256, 2048)), dim3(256), 0, e->stream, f.out.views, (uint32_t)f.nViews, (uint32_t)N, c.used);
+		std::vector<uint32_t> used((size_t)N + 1);
+		HIPCHK(e, hipMemcpyAsync(used.data(), c.used, sizeof(uint32_t) * (N + 1), hipMemcpyDeviceToHost, e->stream));
+		HIPCHK(e, hipStreamSynchronize(e->stream));
+		if (used[(size_t)N]) { e->err = "cloud_finish: a point lists a view outside the scene"; return PMHIP_E_STATE; }
+		for (int i = 0; i < N; ++i)
+			if (used[(size_t)i] && (f.hasBgr.empty() || !f.hasBgr[(size_t)i] || !(e->views[i].sw ? (const void*)e->views[i].oBgr : (const void*)f.bgr))) {
+				e->err = "cloud_finish: bEstimateColor needs pmhip_scene_set_color for every view the points list"; return PMHIP_E_STATE; }
+		if (!f.out.colors) HIPCHK(e, hipMalloc(&f.out.colors, 3 * f.cap));
+		hipLaunchKernelGGL(pmcl_color_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, f.out, n, c.cams, c.imgs);
+		HIPCHK(e, hipGetLastError());
+		HIPCHK(e, hipStreamSynchronize(e->stream));
+		f.haveColor = true;
+		c.ms[3] = ms(t0);
+	}
+	if (wantNormal) {
+		auto t0 = clk::now();
+		const int k = (int)std::min<uint64_t>((uint64_t)p->nNeighbors, f.nPoints);
+		PMClGrid g; rc = buildGrid(e, k, g); if (rc) return rc;
+		c.ms[1] = ms(t0);
+		t0 = clk::now();
+		if (!f.out.normals) HIPCHK(e, hipMalloc(&f.out.normals, sizeof(float) * 3 * f.cap));
+		PMClKnnOut o; memset(&o, 0, sizeof(o));
+		o.normals = f.out.normals; o.viewStart = f.out.viewStart; o.views = f.out.views; o.cams = c.cams;
+		rc = launchKnn(e, true, g, k, n, o); if (rc) return rc;
+		HIPCHK(e, hipStreamSynchronize(e->stream));
+		f.haveNormal = true;
+		c.ms[2] = ms(t0);
+	}
+	if (nPoints) *nPoints = f.nPoints;
+	if (nViews) *nViews = f.nViews;
+	return 0;
+}
+
+int pmhip_scene_cloud_times(pmhip_engine* e, double ms[4]) {
+	if (!e || !ms) return PMHIP_E_ARG;
+	for (int i = 0; i < 4; ++i) ms[i] = e->cl.ms[i];
+	return 0;
+}
 
 } // extern "C"

@@ -423,6 +423,34 @@ def fuse_depth_maps(engine, scene, opt=None, bgr=None) -> dict:
     return engine.scene_fuse(fuse_order(scene), n_min, f_depth, f_normal, want_color, normals == 2)
 
 
+def finish_point_cloud(engine, scene_or_archive, opt, crop_to_roi: bool = False, border_roi: float = 0.0, cloud: dict | None = None) -> dict | None:
+    """The last block of `Scene::DenseReconstruction` (SceneDensify.cpp:1724-1737) on the engine's resident cloud: `RemovePointsOutside(ROI)` when `crop_to_roi` and the
+    scene is bounded (the ROI enlarged by `border_roi`: > 0 EnlargePercent, < 0 Enlarge(-border_roi)), then `EstimatePointColors` if `opt.nEstimateColors == 1` and the
+    cloud has no colours, then `EstimatePointNormals` (k = 16) if `opt.nEstimateNormals == 1` and it has no normals.  The application crops by default
+    (`--crop-to-roi 1`); here it is opt-in.  `scene_or_archive`: the `SceneViews` (its `bgr` images feed the colours), an `mvsi` scene (its OBB is the ROI), or a
+    (SceneViews, mvsi scene) pair.  `cloud`: the resident cloud as last returned, handed back unchanged when there is nothing to do.  Returns the finished cloud."""
+    parts = scene_or_archive if isinstance(scene_or_archive, tuple) else (scene_or_archive,)
+    views = next((p for p in parts if p is not None and hasattr(p, "bgr")), None)
+    archive = next((p for p in parts if p is not None and hasattr(p, "obb_rot")), None)
+    colors = opt is not None and int(opt.nEstimateColors) == 1 and (cloud is None or cloud.get("colors") is None)
+    normals = opt is not None and int(opt.nEstimateNormals) == 1 and (cloud is None or cloud.get("normals") is None)
+    obb = archive._obb() if crop_to_roi and archive is not None and archive.is_bounded() else None
+    if cloud is not None and cloud.get("nPoints", 0) == 0:
+        return cloud                                                  # the reference skips the block for an empty cloud
+    if obb is None and not colors and not normals:
+        return cloud
+    if colors:
+        if views is None:
+            raise ValueError("finish_point_cloud: colours need the SceneViews with the images")
+        for i in range(len(views.gray) - len(getattr(views, "alias_of", {}))):
+            engine.scene_set_color(i, views.bgr[i])
+    out = engine.scene_cloud_finish(crop_obb=obb, border_roi=float(border_roi), estimate_colors=colors, estimate_normals=normals)
+    out.setdefault("nDepths", (cloud or {}).get("nDepths", 0))
+    if cloud is not None and "rounds" in cloud:
+        out["rounds"] = cloud["rounds"]
+    return out
+
+
 def save_dense_scene(mvs_in: str, mvs_out: str, cloud: dict, scene=None, version: int | None = None) -> None:
     """What `DensifyPointCloud` leaves behind as `<scene>_dense.mvs` (`Scene::SaveInterface`, libs/MVS/Scene.cpp:218-300): the input archive with the fused cloud in place
     of the sparse points -- position, the images that see the point with the fusion weight as `confidence`, normal, colour (Col3: B, G, R) -- and, when `scene`
@@ -446,12 +474,15 @@ def save_dense_scene(mvs_in: str, mvs_out: str, cloud: dict, scene=None, version
     mvsi.save(mvs_out, sc, version=version)
 
 
-def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None, **load_args):
+def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None,
+                         crop_to_roi: bool = False, border_roi: float = 0.0, **load_args):
     """`Scene::DenseReconstruction(nFusionMode)` (libs/MVS/SceneDensify.cpp:1655-1750) for the PatchMatch path on one engine: prepare the views (`load_scene`), estimate all
     depth maps with the geometric rounds and the filters the option table asks for (`compute_depth_maps`; with `dmap_dir` under the reference's file contract), and -- unless
     `fusion_mode` is 1, "export depth maps only" -- fuse them and write `<scene>_dense.mvs` to `mvs_out`.  `opt`: an `optdense.OptDense` (default: the table's defaults with the
     application's own `--number-views 8`, `--estimate-normals 2`, `--number-views-fuse` left at the table's 2); `load_args` go to `load_scene` (image_loader,
-    view_neighbors_file, ignore_mask_label, mask_path, mask_loader).  The SGM modes (-1, -2) are openmvs_amd.sgm_pipeline's.  Returns (SceneViews, cloud or None)."""
+    view_neighbors_file, ignore_mask_label, mask_path, mask_loader).  The SGM modes (-1, -2) are openmvs_amd.sgm_pipeline's.  After the fusion the cloud is finished
+    (`finish_point_cloud`): `crop_to_roi` / `border_roi` as the application's `--crop-to-roi` (default 1 there, off here) / `--border-roi`, colours and normals of modes 1.
+    Returns (SceneViews, cloud or None)."""
     from . import optdense
     if fusion_mode not in (0, 1):
         raise ValueError("fusion_mode %d: the PatchMatch path is modes 0 (estimate + fuse) and 1 (depth maps only)" % fusion_mode)
@@ -466,6 +497,8 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     if fusion_mode == 1:
         return sv, None
     cloud = fuse_depth_maps(engine, sv, opt, bgr=sv.bgr)
+    from . import mvsi
+    cloud = finish_point_cloud(engine, (sv, mvsi.load(mvs_in) if crop_to_roi else None), opt, crop_to_roi, border_roi, cloud=cloud)
     if mvs_out:
         save_dense_scene(mvs_in, mvs_out, cloud, sv)
     return sv, cloud

@@ -365,7 +365,8 @@ class EngineRank:
         return self.eng.scene_get_maps(self.slot[g])
 
 
-def dense_reconstruction(engine, scene, opt, world: int = 1, rank: int = 0, seed: int = 0, root: int = 0, device="cpu", fuse_engine=None):
+def dense_reconstruction(engine, scene, opt, world: int = 1, rank: int = 0, seed: int = 0, root: int = 0, device="cpu", fuse_engine=None,
+                         archive=None, crop_to_roi: bool = False, border_roi: float = 0.0):
     """The PatchMatch path of `Scene::DenseReconstruction` (libs/MVS/SceneDensify.cpp:1655-1750) over `world` ranks, one engine each: every rank estimates its block of
     reference views (photometric pass, geometric rounds with the neighbour-only exchange), runs the per-map filters on its own maps and the cross-view filter against its
     neighbours' unfiltered maps; the fusing rank `root` then collects depth, normal and confidence maps view by view and fuses them (FuseDepthMaps is sequential over the
@@ -373,7 +374,8 @@ def dense_reconstruction(engine, scene, opt, world: int = 1, rank: int = 0, seed
 
     scene: a `densify.SceneViews` (every rank runs `densify.load_scene` on the same archive; a rank's engine is handed only the images it holds); its views may differ in size
     and read resampled copies of their neighbours (`alias_of`, ViewData::ScaleImage); opt: an `optdense.OptDense`; fuse_engine: the engine `root` fuses on (default:
-    `engine`, whose compact scene is replaced by the whole one).  Returns the cloud on `root`, None elsewhere."""
+    `engine`, whose compact scene is replaced by the whole one).  The fusing rank finishes the cloud (`densify.finish_point_cloud`: colours / normals of modes 1, and the
+    crop to the ROI of `archive`, an `mvsi` scene, when `crop_to_roi`).  Returns the cloud on `root`, None elsewhere."""
     from . import densify
     alias_of = dict(getattr(scene, "alias_of", None) or {})
     n = len(scene.gray) - len(alias_of)                                         # the images; the resampled copies follow them as source-only slots
@@ -408,4 +410,5 @@ def dense_reconstruction(engine, scene, opt, world: int = 1, rank: int = 0, seed
             fe.scene_set_view(v, None, scene.K[v], scene.R[v], scene.C[v], float(scene.dmin[v]), float(scene.dmax[v]), scene.neighbors[v])
         fe.scene_set_maps(v, maps["depth"][v].cpu().numpy(), maps["normal"][v].cpu().numpy())
         fe.scene_set_conf(v, maps["conf"][v].cpu().numpy())
-    return densify.fuse_depth_maps(fe, scene, opt, bgr=scene.bgr)
+    cloud = densify.fuse_depth_maps(fe, scene, opt, bgr=scene.bgr)
+    return densify.finish_point_cloud(fe, (scene, archive), opt, crop_to_roi, border_roi, cloud=cloud)

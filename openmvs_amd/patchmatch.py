@@ -51,14 +51,19 @@ class PMHipFuseParams(C.Structure):
                 ("bEstimateColor", C.c_int32), ("bEstimateNormal", C.c_int32)]
 
 
-PMHIP_ABI_VERSION = 6      # include/pmhip.h
+class PMHipCloudParams(C.Structure):
+    _fields_ = [("bCrop", C.c_int32), ("obbRot", C.c_float * 9), ("obbPos", C.c_float * 3), ("obbExt", C.c_float * 3), ("fBorderROI", C.c_float),
+                ("bEstimateColor", C.c_int32), ("bEstimateNormal", C.c_int32), ("nNeighbors", C.c_int32)]
+
+
+PMHIP_ABI_VERSION = 7      # include/pmhip.h
 
 
 class PMHipTuning(C.Structure):
     _fields_ = [("viewGroups", C.c_int32), ("wideMaxViews", C.c_int32), ("wideHyps", C.c_int32), ("sweepLanes", C.c_int32), ("quadBuffer", C.c_int32), ("widePixels", C.c_int32), ("wide8Pixels", C.c_int32), ("reserved0", C.c_int32)]
 
 
-EXPORTS = ["pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
+EXPORTS = ["pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_scene_cloud_finish", "pmhip_scene_cloud_set", "pmhip_scene_cloud_knn", "pmhip_scene_cloud_times", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
            "pmhip_estimate_depth_map", "pmhip_estimate_depth_map_masked", "pmhip_last_error", "pmhip_scene_create", "pmhip_scene_set_view",
            "pmhip_scene_estimate", "pmhip_scene_commit_round", "pmhip_scene_reset_view", "pmhip_scene_set_maps",
            "pmhip_scene_get_maps", "pmhip_scene_device_ptr", "pmhip_scene_copy", "pmhip_scene_filter", "pmhip_scene_filter_commit", "pmhip_scene_gap_interpolation", "pmhip_scene_remove_small_segments", "pmhip_scene_images_updated", "pmhip_scene_maps_updated", "pmhip_scene_bytes", "pmhip_sync",
@@ -342,6 +347,62 @@ class PatchMatchHIP:
                                                  vp(projs, C.c_uint16), vp(cols, C.c_uint8), vp(nrm, C.c_float)))
         return dict(nPoints=P, nDepths=int(nD.value), points=pts, viewStart=vs, views=views, weights=wts, projs=projs, colors=cols, normals=nrm,
                     rounds=int(self._lib.pmhip_scene_fuse_rounds(self._h)))
+
+    def scene_cloud_get(self):
+        """The resident cloud (after scene_fuse, scene_cloud_set or scene_cloud_finish) in the layout of scene_fuse's result; colors / normals are None when the
+        cloud has none."""
+        nP, nV = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.pmhip_scene_cloud_finish(self._h, C.byref(PMHipCloudParams()), C.byref(nP), C.byref(nV)))
+        P, V = int(nP.value), int(nV.value)
+        pts = np.zeros((P, 3), np.float32); vs = np.zeros(P + 1, np.uint32); views = np.zeros(V, np.uint32); wts = np.zeros(V, np.float32)
+        projs = np.zeros((V, 2), np.uint16)
+        vp = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))
+        self._chk(self._lib.pmhip_scene_fuse_get(self._h, vp(pts, C.c_float), vp(vs, C.c_uint32), vp(views, C.c_uint32), vp(wts, C.c_float), vp(projs, C.c_uint16), None, None))
+        cols = np.zeros((P, 3), np.uint8); nrm = np.zeros((P, 3), np.float32)
+        if self._lib.pmhip_scene_fuse_get(self._h, None, None, None, None, None, vp(cols, C.c_uint8), None) != 0:
+            cols = None
+        if self._lib.pmhip_scene_fuse_get(self._h, None, None, None, None, None, None, vp(nrm, C.c_float)) != 0:
+            nrm = None
+        return dict(nPoints=P, points=pts, viewStart=vs, views=views, weights=wts, projs=projs, colors=cols, normals=nrm)
+
+    def scene_cloud_finish(self, crop_obb=None, border_roi=0.0, estimate_colors=False, estimate_normals=False, n_neighbors=16):
+        """The last block of Scene::DenseReconstruction on the resident cloud (pmhip_scene_cloud_finish): crop to `crop_obb` = (rot 3x3, pos 3, ext 3) of
+        TOBB<float,3> (None: no crop) enlarged by `border_roi`, then colours and PCA normals (each only if the cloud has none).  Returns scene_cloud_get()
+        plus the step times in ms (`times`: crop, grid, knn_pca, colors)."""
+        prm = PMHipCloudParams()
+        if crop_obb is not None:
+            rot, pos, ext = crop_obb
+            prm.bCrop = 1
+            prm.obbRot[:] = [float(v) for v in np.asarray(rot, np.float32).ravel()]
+            prm.obbPos[:] = [float(v) for v in np.asarray(pos, np.float32).ravel()]
+            prm.obbExt[:] = [float(v) for v in np.asarray(ext, np.float32).ravel()]
+        prm.fBorderROI = float(border_roi)
+        prm.bEstimateColor = 1 if estimate_colors else 0
+        prm.bEstimateNormal = 1 if estimate_normals else 0
+        prm.nNeighbors = int(n_neighbors)
+        self._chk(self._lib.pmhip_scene_cloud_finish(self._h, C.byref(prm), None, None))
+        t = (C.c_double * 4)()
+        self._chk(self._lib.pmhip_scene_cloud_times(self._h, t))
+        out = self.scene_cloud_get()
+        out["times"] = dict(crop=t[0], grid=t[1], knn_pca=t[2], colors=t[3])
+        return out
+
+    def scene_cloud_set(self, points, viewStart, views, weights=None):
+        """Replace the resident cloud (pmhip_scene_cloud_set); views are image indices of the loaded scene."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        vs = np.ascontiguousarray(viewStart, np.uint32); vv = np.ascontiguousarray(views, np.uint32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+        if len(vs) != len(pts) + 1:
+            raise ValueError("viewStart must have nPoints + 1 entries")
+        self._chk(self._lib.pmhip_scene_cloud_set(self._h, _fp(pts), vs.ctypes.data_as(C.POINTER(C.c_uint32)), vv.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  None if w is None else _fp(w), C.c_uint64(len(pts))))
+
+    def scene_cloud_knn(self, queries, k=16):
+        """The k nearest points of the resident cloud for each query index, nearest first (pmhip_scene_cloud_knn): (nq, k) uint32."""
+        q = np.ascontiguousarray(queries, np.uint32)
+        out = np.zeros((len(q), int(k)), np.uint32)
+        self._chk(self._lib.pmhip_scene_cloud_knn(self._h, int(k), q.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint32(len(q)), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     def scene_copy(self, what, first, count, device_ptr, to_engine):
         self._chk(self._lib.pmhip_scene_copy(self._h, what, first, count, C.c_void_p(device_ptr), 1 if to_engine else 0))
