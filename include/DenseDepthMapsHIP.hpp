@@ -186,6 +186,31 @@ public:
 		                         color ? pc.colors.data() : nullptr, normal ? pc.normals.data() : nullptr));
 	}
 
+	// Scene::PointCloudFilter(thRemove) (--filter-point-cloud, SceneDensify.cpp:2225-2359) on the cloud FuseDepthMaps / FinishPointCloud left on the device, after
+	// PointCloud::RemoveMinViews(nMinViews) when nMinViews > 0: the visibility vote over the loaded scene's cameras at each view's own width, then the reference's
+	// backward swap-remove loop.  The application runs it for thRemove < 0; any value is taken here.  `pc` is replaced by the filtered cloud; `visibility`, when
+	// given, receives the votes, indexed as the cloud was before the visibility removal.
+	void FilterPointCloud(PointCloud& pc, int thRemove, unsigned nMinViews = 0, std::vector<int32_t>* visibility = nullptr) { FilterOn(e_, pc, thRemove, nMinViews, visibility); }
+	static void FilterOn(pmhip_engine* e, PointCloud& pc, int thRemove, unsigned nMinViews, std::vector<int32_t>* visibility) {
+		auto chk = [e](int rc) { if (rc != PMHIP_OK) throw std::runtime_error(std::string("pmhip: ") + pmhip_last_error(e)); };
+		if (visibility) visibility->clear();
+		if (pc.size() == 0) return;
+		PMHipCloudFilterParams p;
+		memset(&p, 0, sizeof(p));
+		uint64_t nP = pc.size(), nV = 0;
+		if (nMinViews > 0) { p.nMinViews = nMinViews; chk(pmhip_scene_cloud_filter(e, &p, &nP, &nV)); p.nMinViews = 0; }   // (on its own: nP is then the size of the vote)
+		const uint64_t nVote = nP;
+		p.bVisibility = 1; p.thRemove = thRemove;
+		chk(pmhip_scene_cloud_filter(e, &p, &nP, &nV));
+		if (visibility && nVote) { visibility->assign((size_t)nVote, 0); chk(pmhip_scene_cloud_visibility(e, visibility->data(), nVote)); }
+		const bool color = !pc.colors.empty(), normal = !pc.normals.empty();
+		pc.points.assign((size_t)nP * 3, 0.f); pc.viewStart.assign((size_t)nP + 1, 0u); pc.views.assign((size_t)nV, 0u); pc.weights.assign((size_t)nV, 0.f);
+		pc.projs.assign((size_t)nV * 2, (uint16_t)0);
+		pc.colors.assign(color ? (size_t)nP * 3 : 0, (unsigned char)0); pc.normals.assign(normal ? (size_t)nP * 3 : 0, 0.f);
+		chk(pmhip_scene_fuse_get(e, pc.points.data(), pc.viewStart.data(), pc.views.data(), pc.weights.data(), pc.projs.data(),
+		                         color ? pc.colors.data() : nullptr, normal ? pc.normals.data() : nullptr));
+	}
+
 	// One view's maps back to the host (any pointer may be null); ViewWidth(idx) x ViewHeight(idx) entries
 	void GetMaps(int idx, float* depth, float* normal, float* conf) { check(pmhip_scene_get_maps(e_, idx, depth, normal, conf)); }
 	int ViewWidth(int idx) const { return views_[(size_t)idx].w > 0 ? views_[(size_t)idx].w : w_; }

@@ -174,6 +174,10 @@ public:
 	void FinishPointCloud(PointCloud& pc, const DenseDepthMapsHIP::OBB& roi, bool bCrop2ROI, float fBorderROI) {
 		DenseDepthMapsHIP::FinishOn(eng_[0], opt_, pc, roi, bCrop2ROI, fBorderROI);
 	}
+	// Scene::PointCloudFilter / RemoveMinViews on the fusing device: see DenseDepthMapsHIP::FilterPointCloud
+	void FilterPointCloud(PointCloud& pc, int thRemove, unsigned nMinViews = 0, std::vector<int32_t>* visibility = nullptr) {
+		DenseDepthMapsHIP::FilterOn(eng_[0], pc, thRemove, nMinViews, visibility);
+	}
 	// a view's maps from the device that owns it; ViewWidth(idx) x ViewHeight(idx) entries
 	int ViewWidth(int idx) const { return sized(idx) ? views_[(size_t)idx].w : w_; }
 	int ViewHeight(int idx) const { return sized(idx) ? views_[(size_t)idx].h : h_; }

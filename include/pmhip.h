@@ -224,6 +224,38 @@ int pmhip_scene_cloud_set(pmhip_engine* e, const float* points, const uint32_t* 
 int pmhip_scene_cloud_knn(pmhip_engine* e, int nNeighbors, const uint32_t* queries, uint32_t nQueries, uint32_t* out);
 /* Milliseconds of the steps of the last pmhip_scene_cloud_finish, each ended by a stream synchronisation: crop, grid build, k-NN + PCA, colours. */
 int pmhip_scene_cloud_times(pmhip_engine* e, double ms[4]);
+/* Scene::PointCloudFilter(thRemove) (--filter-point-cloud, SceneDensify.cpp:2225-2359) and PointCloud::RemoveMinViews (--export-number-views -N,
+ * PointCloud.cpp:88-93) on the resident cloud.  nMinViews > 0 first removes the points with fewer views; bVisibility then votes on what is left: for
+ * every point i and every view v it lists, the cone from Cast<float>(C_v) through the point with half-angle angle_v and height 1.02 x distance
+ * classifies EVERY point j of the cloud (TConeIntersect::Classify in float, not depth-similar within 1 %): visibility[j] += views(j) behind the point,
+ * -= views(i) in front of it; points with visibility <= thRemove are removed.  Both removals are the reference's backward swap-remove loop, for
+ * points, views, weights, projections, colours and normals.  The vote is the sum over all points j (the reference's octree computes that sum up to the
+ * float rounding of its conservative cell pruning); the angular bins it runs on never change it (csrc/pm_cloud_filter.hip).
+ * camC (3 doubles per camera) / camAngle (radians per camera), nCams of each, or both NULL: the loaded scene's C and 2 atan(w / (2 K00)) / w at each
+ * view's own width.  Nothing else of a scene is read, so with them the call works in an engine that holds no images.  A new struct beside the others:
+ * PMHIP_ABI_VERSION stays 7. */
+typedef struct PMHipCloudFilterParams {
+	int32_t bVisibility;                     /* run the visibility vote and remove visibility <= thRemove */
+	int32_t thRemove;                        /* the application passes it only when negative; any value here */
+	uint32_t nMinViews;                      /* > 0: RemoveMinViews(nMinViews) first */
+	int32_t nCams;                           /* cameras in camC / camAngle */
+	const double* camC; const float* camAngle;
+} PMHipCloudFilterParams;
+/* pmhip_scene_cloud_set with optional colours (3 bytes BGR per point) and normals (3 floats per point), either may be NULL; nCams > 0 replaces the
+ * loaded scene's image count in the range check of the view indices, so that an archive's cloud can be installed in an engine without a scene. */
+int pmhip_scene_cloud_load(pmhip_engine* e, const float* points, const uint32_t* viewStart, const uint32_t* views, const float* weights,
+                           const unsigned char* colors, const float* normals, uint64_t nPoints, int32_t nCams);
+/* nPoints / nViews: the sizes after the removal (either may be NULL); pmhip_scene_fuse_get returns the cloud.  An empty cloud is a no-op; a point
+ * that lists a view outside the cameras is PMHIP_E_STATE. */
+int pmhip_scene_cloud_filter(pmhip_engine* e, const PMHipCloudFilterParams* p, uint64_t* nPoints, uint64_t* nViews);
+/* The votes of the last filter, indexed as the cloud was before the visibility removal (n = that size; after nMinViews, if given). */
+int pmhip_scene_cloud_visibility(pmhip_engine* e, int32_t* out, uint64_t n);
+/* The cone constants the last filter used, per camera: angle, cosAngleSq = SQUARE(cosf(angle)) (cosf on the host); 0, 0 for a view that is not set. */
+int pmhip_scene_cloud_filter_cones(pmhip_engine* e, float* out /* nCams x 2 */);
+/* Milliseconds of the last filter, each part ended by a stream synchronisation and summed over the views: binning, cone pass, removal. */
+int pmhip_scene_cloud_filter_times(pmhip_engine* e, double ms[3]);
+/* Diagnostic: the cones of the last filter ((point, view) pairs) and the candidates classified against them, summed. */
+int pmhip_scene_cloud_filter_counts(pmhip_engine* e, uint64_t out[2]);
 /* Device-to-device copy between a caller buffer (e.g. a torch tensor used for an RCCL collective)
  * and `count` consecutive views of one per-kind array, starting at view firstIdx; `what` as above.
  * toEngine != 0 copies caller -> engine.  Asynchronous on the engine stream. */

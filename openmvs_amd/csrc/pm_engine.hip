@@ -11,6 +11,7 @@
 #include "pm_filter.hip"
 #include "pm_fuse.hip"
 #include "pm_cloud.hip"
+#include "pm_cloud_filter.hip"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -169,6 +170,9 @@ struct pmhip_engine {
 		uint32_t *qbuf = nullptr, *obuf = nullptr; size_t qCap = 0;
 		uint32_t* misc = nullptr; float* sample = nullptr;       // misc: scan totals [0..3], jump flag [4], bounding box [8..13]
 		double ms[4] = {0, 0, 0, 0};
+		// the visibility filter (pm_cloud_filter.hip): votes of the last filter (indexed as the cloud was before its removal), views in use, cone constants, step times
+		int* vis = nullptr; size_t visCap = 0; uint64_t visN = 0; uint32_t* fused = nullptr; int fusedCap = 0;
+		std::vector<float> cones; double fms[3] = {0, 0, 0}; unsigned long long* fstats = nullptr; uint64_t fcount[2] = {0, 0};
 	} cl;
 	// batch scratch (grow only)
 	int batchCap = 0;
@@ -218,7 +222,7 @@ static void freeFuse(pmhip_engine* e) {
 static void freeCloud(pmhip_engine* e) {
 	auto& c = e->cl;
 	void* ptrs[] = {c.alt.points, c.alt.viewStart, c.alt.views, c.alt.weights, c.alt.projs, c.alt.colors, c.alt.normals, c.hole, c.nxt, c.cellOf, c.spts,
-	                c.tileSums, c.tileOff, c.counts, c.cellStart, c.cams, c.imgs, c.used, c.qbuf, c.obuf, c.misc, c.sample};
+	                c.tileSums, c.tileOff, c.counts, c.cellStart, c.cams, c.imgs, c.used, c.qbuf, c.obuf, c.misc, c.sample, c.vis, c.fused, c.fstats};
 	for (void* q : ptrs) if (q) hipFree(q);
 	c = pmhip_engine::Cloud{};
 }
@@ -1781,14 +1785,13 @@ static int launchKnn(pmhip_engine* e, bool pca, const PMClGrid& g, int k, uint32
 	return 0;
 }
 
-// PointCloud::RemovePointsOutside on the resident cloud (see pm_cloud.hip for the order)
-static int cropCloud(pmhip_engine* e, const PMClObb& box) {
+// The RFOREACH + RemovePoint loop of the reference (PointCloud.cpp:66-93) on the resident cloud, see pm_cloud.hip for the order.  The caller has called
+// ensureCloudPoints, cleared misc[0..3] and launched the kernel that writes the hole flags (c.hole) and the holes per tile (c.tileSums) of the n points:
+// pmcl_crop_flags for the ROI, pmclf_flags for the visibility filter and RemoveMinViews.
+static int removeFlagged(pmhip_engine* e) {
 	auto& c = e->cl; auto& f = e->fu;
 	const uint32_t n = (uint32_t)f.nPoints;
-	int rc = ensureCloudPoints(e, n); if (rc) return rc;
 	const unsigned nT = (n + PMCL_TILE - 1) / PMCL_TILE;
-	HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
-	hipLaunchKernelGGL(pmcl_crop_flags, dim3(nT), dim3(PMCL_TB), 0, e->stream, f.out.points, n, box, c.hole, c.tileSums);
 	hipLaunchKernelGGL(pmfu_scan_tiles, dim3(1), dim3(1024), 0, e->stream, c.tileSums, nT, c.misc, c.tileOff);
 	hipLaunchKernelGGL(pmcl_crop_next, dim3(nT), dim3(PMCL_TB), 0, e->stream, c.hole, n, c.tileOff, c.misc, c.nxt);
 	uint32_t H = 0;
@@ -1837,6 +1840,16 @@ static int cropCloud(pmhip_engine* e, const PMClObb& box) {
 	std::swap(f.out, c.alt); std::swap(f.cap, c.altCap);
 	f.nPoints = m; f.nViews = nv;
 	return 0;
+}
+
+// PointCloud::RemovePointsOutside
+static int cropCloud(pmhip_engine* e, const PMClObb& box) {
+	auto& c = e->cl; auto& f = e->fu;
+	const uint32_t n = (uint32_t)f.nPoints;
+	int rc = ensureCloudPoints(e, n); if (rc) return rc;
+	HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
+	hipLaunchKernelGGL(pmcl_crop_flags, dim3((n + PMCL_TILE - 1) / PMCL_TILE), dim3(PMCL_TB), 0, e->stream, f.out.points, n, box, c.hole, c.tileSums);
+	return removeFlagged(e);
 }
 
 int pmhip_scene_cloud_set(pmhip_engine* e, const float* points, const uint32_t* viewStart, const uint32_t* views, const float* weights, uint64_t nPoints) {
@@ -1952,6 +1965,173 @@ int pmhip_scene_cloud_finish(pmhip_engine* e, const PMHipCloudParams* p, uint64_
 int pmhip_scene_cloud_times(pmhip_engine* e, double ms[4]) {
 	if (!e || !ms) return PMHIP_E_ARG;
 	for (int i = 0; i < 4; ++i) ms[i] = e->cl.ms[i];
+	return 0;
+}
+
+
+// ---- Scene::PointCloudFilter / PointCloud::RemoveMinViews on the resident cloud (pm_cloud_filter.hip) ------------------------------------
+int pmhip_scene_cloud_load(pmhip_engine* e, const float* points, const uint32_t* viewStart, const uint32_t* views, const float* weights, const unsigned char* colors, const float* normals,
+                           uint64_t nPoints, int32_t nCams) {
+	if (!e || !viewStart || nCams < 0 || (nPoints && (!points || !views))) return PMHIP_E_ARG;
+	const int N = nCams > 0 ? nCams : e->nImages;
+	if (N < 1) { e->err = "cloud_load: no scene and no camera count"; return PMHIP_E_STATE; }
+	if (nPoints >= 0xFFFFFFFFull || viewStart[0] != 0) { e->err = "cloud_load: bad sizes"; return PMHIP_E_ARG; }
+	const uint64_t nV = viewStart[nPoints];
+	for (uint64_t i = 0; i < nPoints; ++i) if (viewStart[i + 1] <= viewStart[i]) { e->err = "cloud_load: every point needs a view"; return PMHIP_E_ARG; }
+	for (uint64_t v = 0; v < nV; ++v) if (views[v] >= (uint32_t)N) { e->err = "cloud_load: view index outside the cameras"; return PMHIP_E_ARG; }
+	HIPCHK(e, hipSetDevice(e->device));
+	auto& f = e->fu;
+	const size_t cap = (size_t)std::max<uint64_t>(nPoints, nV) + 1;
+	if (f.cap < cap || !f.out.points) {
+		freeFuseOut(e);
+		HIPCHK(e, hipMalloc(&f.out.points, sizeof(float) * 3 * cap)); HIPCHK(e, hipMalloc(&f.out.viewStart, sizeof(uint32_t) * (cap + 1)));
+		HIPCHK(e, hipMalloc(&f.out.views, sizeof(uint32_t) * cap)); HIPCHK(e, hipMalloc(&f.out.weights, sizeof(float) * cap));
+		HIPCHK(e, hipMalloc(&f.out.projs, sizeof(uint16_t) * 2 * cap));
+		f.cap = cap;
+	}
+	if (colors && !f.out.colors) HIPCHK(e, hipMalloc(&f.out.colors, 3 * f.cap));
+	if (normals && !f.out.normals) HIPCHK(e, hipMalloc(&f.out.normals, sizeof(float) * 3 * f.cap));
+	if (nPoints) {
+		HIPCHK(e, hipMemcpyAsync(f.out.points, points, sizeof(float) * 3 * nPoints, hipMemcpyHostToDevice, e->stream));
+		if (colors) HIPCHK(e, hipMemcpyAsync(f.out.colors, colors, 3 * nPoints, hipMemcpyHostToDevice, e->stream));
+		if (normals) HIPCHK(e, hipMemcpyAsync(f.out.normals, normals, sizeof(float) * 3 * nPoints, hipMemcpyHostToDevice, e->stream));
+	}
+	HIPCHK(e, hipMemcpyAsync(f.out.viewStart, viewStart, sizeof(uint32_t) * (nPoints + 1), hipMemcpyHostToDevice, e->stream));
+	if (nV) {
+		HIPCHK(e, hipMemcpyAsync(f.out.views, views, sizeof(uint32_t) * nV, hipMemcpyHostToDevice, e->stream));
+		if (weights) HIPCHK(e, hipMemcpyAsync(f.out.weights, weights, sizeof(float) * nV, hipMemcpyHostToDevice, e->stream));
+		else HIPCHK(e, hipMemsetAsync(f.out.weights, 0, sizeof(float) * nV, e->stream));
+		HIPCHK(e, hipMemsetAsync(f.out.projs, 0, sizeof(uint16_t) * 2 * nV, e->stream));
+	}
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	f.nPoints = nPoints; f.nViews = nV; f.nDepths = 0; f.rounds = 0; f.haveColor = colors != nullptr; f.haveNormal = normals != nullptr;
+	return 0;
+}
+
+// hole flags from the votes (vis) or the view counts, then the removal
+static int removeByFlags(pmhip_engine* e, const int* vis, int th, uint32_t nMin) {
+	auto& c = e->cl; auto& f = e->fu;
+	const uint32_t n = (uint32_t)f.nPoints;
+	int rc = ensureCloudPoints(e, n); if (rc) return rc;
+	HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
+	hipLaunchKernelGGL(pmclf_flags, dim3((n + PMCL_TILE - 1) / PMCL_TILE), dim3(PMCL_TB), 0, e->stream, vis, th, f.out.viewStart, nMin, n, c.hole, c.tileSums);
+	return removeFlagged(e);
+}
+
+int pmhip_scene_cloud_filter(pmhip_engine* e, const PMHipCloudFilterParams* p, uint64_t* nPoints, uint64_t* nViews) {
+	if (!e || !p) return PMHIP_E_ARG;
+	auto& f = e->fu; auto& c = e->cl;
+	if (!f.out.points) { e->err = "cloud_filter: no cloud (pmhip_scene_fuse, pmhip_scene_cloud_set or pmhip_scene_cloud_load first)"; return PMHIP_E_STATE; }
+	if ((p->camC != nullptr) != (p->camAngle != nullptr) || (p->camC && p->nCams < 1)) { e->err = "cloud_filter: camC and camAngle go together, with nCams > 0"; return PMHIP_E_ARG; }
+	HIPCHK(e, hipSetDevice(e->device));
+	for (double& t : c.fms) t = 0;
+	c.visN = 0; c.cones.clear(); c.fcount[0] = c.fcount[1] = 0;
+	using clk = std::chrono::steady_clock;
+	auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+	int rc = 0;
+	if (p->nMinViews > 0 && f.nPoints) {                               // PointCloud::RemoveMinViews
+		const auto t0 = clk::now();
+		rc = removeByFlags(e, nullptr, 0, p->nMinViews); if (rc) return rc;
+		c.fms[2] += ms(t0);
+	}
+	if (p->bVisibility && f.nPoints) {
+		const int N = p->camC ? p->nCams : e->nImages;
+		if (N < 1) { e->err = "cloud_filter: no scene and no cameras"; return PMHIP_E_STATE; }
+		const uint32_t n = (uint32_t)f.nPoints;
+		// the views in use; a point that lists a view outside the cameras is a caller error
+		if (c.fusedCap < N + 1) { CLALLOC(e, c.fused, sizeof(uint32_t) * (N + 1)); c.fusedCap = N + 1; }
+		HIPCHK(e, hipMemsetAsync(c.fused, 0, sizeof(uint32_t) * (N + 1), e->stream));
+		hipLaunchKernelGGL(pmcl_mark_views, dim3((unsigned)std::min<uint64_t>((f.nViews + 255) / 256, 2048)), dim3(256), 0, e->stream, f.out.views, (uint32_t)f.nViews, (uint32_t)N, c.fused);
+		std::vector<uint32_t> used((size_t)N + 1);
+		HIPCHK(e, hipMemcpyAsync(used.data(), c.fused, sizeof(uint32_t) * (N + 1), hipMemcpyDeviceToHost, e->stream));
+		HIPCHK(e, hipStreamSynchronize(e->stream));
+		if (used[(size_t)N]) { e->err = "cloud_filter: a point lists a view outside the cameras"; return PMHIP_E_STATE; }
+		// the cones: origin Cast<float>(C), angle = float(ComputeFOV(0) / width), cosAngleSq = SQUARE(cosf(angle)) -- on the host, once per view
+		std::vector<PMClfView> V((size_t)N);
+		c.cones.assign((size_t)N * 2, 0.f);
+		for (int i = 0; i < N; ++i) {
+			memset(&V[i], 0, sizeof(PMClfView));
+			const double* C; float angle;
+			if (p->camC) { C = p->camC + 3 * i; angle = p->camAngle[i]; }
+			else {
+				if (!e->views[i].set) { if (used[(size_t)i]) { e->err = "cloud_filter: a point lists a view that is not set"; return PMHIP_E_STATE; } continue; }
+				C = e->views[i].C;
+				const double w = (double)e->vw(i);
+				angle = (float)(2. * atan(w / (2. * e->views[i].K[0])) / w);
+			}
+			const float cs = cosf(angle);
+			V[i].ox = (float)C[0]; V[i].oy = (float)C[1]; V[i].oz = (float)C[2]; V[i].cosSq = cs * cs; V[i].view = (uint32_t)i;
+			pmclf_plan(V[i].cosSq, V[i]);
+			c.cones[(size_t)i * 2] = angle; c.cones[(size_t)i * 2 + 1] = V[i].cosSq;
+		}
+		if (c.visCap < (size_t)n) { CLALLOC(e, c.vis, sizeof(int) * (size_t)n); c.visCap = n; }
+		HIPCHK(e, hipMemsetAsync(c.vis, 0, sizeof(int) * (size_t)n, e->stream));
+		if (!c.fstats) HIPCHK(e, hipMalloc(&c.fstats, sizeof(unsigned long long) * 2));
+		HIPCHK(e, hipMemsetAsync(c.fstats, 0, sizeof(unsigned long long) * 2, e->stream));
+		const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
+		for (int i = 0; i < N; ++i) {
+			if (!used[(size_t)i]) continue;                                  // views that no point lists are skipped
+			auto t0 = clk::now();
+			const uint32_t nBins = 6u * (uint32_t)V[i].R * (uint32_t)V[i].R, nS = nBins + 1;   // one more, empty: binStart[nBins] = n
+			if (c.cellCap < (size_t)nS) { CLALLOC(e, c.counts, sizeof(uint32_t) * nS); CLALLOC(e, c.cellStart, sizeof(uint32_t) * nS); c.cellCap = nS; }
+			rc = ensureCloudPoints(e, n); if (rc) return rc;                 // (the sorted copy, and tiles for the bin scan)
+			HIPCHK(e, hipMemsetAsync(c.counts, 0, sizeof(uint32_t) * nS, e->stream));
+			HIPCHK(e, hipMemsetAsync(c.misc, 0, sizeof(uint32_t) * 4, e->stream));
+			hipLaunchKernelGGL(pmclf_count_kernel, dim3(nb), dim3(256), 0, e->stream, f.out.points, n, V[i], c.cellOf, c.counts);
+			const unsigned nT = (nS + PMCL_TILE - 1) / PMCL_TILE;
+			hipLaunchKernelGGL(pmcl_tile_sums_u32, dim3(nT), dim3(PMCL_TB), 0, e->stream, c.counts, nS, c.tileSums);
+			hipLaunchKernelGGL(pmfu_scan_tiles, dim3(1), dim3(1024), 0, e->stream, c.tileSums, nT, c.misc, c.tileOff);
+			hipLaunchKernelGGL(pmcl_scan_apply, dim3(nT), dim3(PMCL_TB), 0, e->stream, c.counts, nS, c.tileOff, c.cellStart);
+			hipLaunchKernelGGL(pmcl_scatter_kernel, dim3(nb), dim3(256), 0, e->stream, f.out.points, n, c.cellOf, c.counts, c.spts);
+			HIPCHK(e, hipGetLastError());
+			HIPCHK(e, hipStreamSynchronize(e->stream));
+			c.fms[0] += ms(t0);
+			t0 = clk::now();
+			hipLaunchKernelGGL(pmclf_cone_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, V[i], c.spts, c.cellStart, n, f.out.viewStart, f.out.views, c.vis, c.fstats);
+			HIPCHK(e, hipGetLastError());
+			HIPCHK(e, hipStreamSynchronize(e->stream));
+			c.fms[1] += ms(t0);
+		}
+		c.visN = n;
+		unsigned long long st[2] = {0, 0};
+		HIPCHK(e, hipMemcpyAsync(st, c.fstats, sizeof(st), hipMemcpyDeviceToHost, e->stream));
+		HIPCHK(e, hipStreamSynchronize(e->stream));
+		c.fcount[0] = st[0]; c.fcount[1] = st[1];
+		const auto t0 = clk::now();
+		rc = removeByFlags(e, c.vis, p->thRemove, 0u); if (rc) return rc;
+		c.fms[2] += ms(t0);
+	}
+	if (nPoints) *nPoints = f.nPoints;
+	if (nViews) *nViews = f.nViews;
+	return 0;
+}
+
+int pmhip_scene_cloud_visibility(pmhip_engine* e, int32_t* out, uint64_t n) {
+	if (!e || (n && !out)) return PMHIP_E_ARG;
+	if (n != e->cl.visN) { e->err = "cloud_visibility: n is not the size of the cloud the last filter voted on"; return PMHIP_E_ARG; }
+	if (!n) return 0;
+	HIPCHK(e, hipSetDevice(e->device));
+	HIPCHK(e, hipMemcpyAsync(out, e->cl.vis, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	return 0;
+}
+
+int pmhip_scene_cloud_filter_cones(pmhip_engine* e, float* out) {
+	if (!e || !out) return PMHIP_E_ARG;
+	if (e->cl.cones.empty()) { e->err = "cloud_filter_cones: no visibility filter has run"; return PMHIP_E_STATE; }
+	memcpy(out, e->cl.cones.data(), sizeof(float) * e->cl.cones.size());
+	return 0;
+}
+
+int pmhip_scene_cloud_filter_counts(pmhip_engine* e, uint64_t out[2]) {
+	if (!e || !out) return PMHIP_E_ARG;
+	out[0] = e->cl.fcount[0]; out[1] = e->cl.fcount[1];
+	return 0;
+}
+
+int pmhip_scene_cloud_filter_times(pmhip_engine* e, double ms[3]) {
+	if (!e || !ms) return PMHIP_E_ARG;
+	for (int i = 0; i < 3; ++i) ms[i] = e->cl.fms[i];
 	return 0;
 }
 

@@ -474,16 +474,59 @@ def save_dense_scene(mvs_in: str, mvs_out: str, cloud: dict, scene=None, version
     mvsi.save(mvs_out, sc, version=version)
 
 
+def archive_cones(sc):
+    """The cones of `Scene::PointCloudFilter` for an `mvsi` scene: (C (n, 3) double, angle (n,) float32) with angle = float(ComputeFOV(0) / width) and
+    ComputeFOV(0) = 2 atan(width / (2 K00)) at each image's own resolution (Image.cpp:209-213); zeros for an image without a pose."""
+    import numpy as np
+    n = len(sc.images)
+    C = np.zeros((n, 3), np.float64); ang = np.zeros(n, np.float32)
+    for i, im in enumerate(sc.images):
+        if not im.is_valid():
+            continue
+        K, _, Ci, w, _ = sc.camera(i)
+        C[i] = Ci; ang[i] = np.float32(2.0 * np.arctan(float(w) / (2.0 * float(K[0, 0]))) / float(w))
+    return C, ang
+
+
+def filter_point_cloud(engine, mvs_in: str, mvs_out: str | None = None, th_remove: int = -1, min_views: int = 0) -> dict:
+    """The application's modes `--filter-point-cloud th_remove` (DensifyPointCloud.cpp:367-374, `Scene::PointCloudFilter`; run when negative) and
+    `--export-number-views -min_views` (:375-388, `PointCloud::RemoveMinViews`) on an archive: its vertices, view lists, confidences, colours and normals are the
+    cloud, the cameras are taken at each image's own resolution, the cloud is filtered on the engine and the archive is written to `mvs_out` with the fields of
+    `save_dense_scene`.  No image file is read, and the engine needs no scene.  Returns the filtered cloud (`PatchMatchHIP.scene_cloud_filter`)."""
+    import numpy as np
+    from . import mvsi
+    sc = mvsi.load(mvs_in)
+    P = len(sc.vertices)
+    C, ang = archive_cones(sc)
+    col = sc.vertices_color if len(sc.vertices_color) == P and P else None
+    nrm = sc.vertices_normal if len(sc.vertices_normal) == P and P else None
+    engine.scene_cloud_load(sc.vertices, np.asarray(sc.vertex_view_start, np.uint32), sc.vertex_views["image_id"], sc.vertex_views["confidence"], col, nrm, n_cams=len(sc.images))
+    out = engine.scene_cloud_filter(th_remove=int(th_remove) if th_remove < 0 else None, min_views=int(min_views), cam_C=C, cam_angle=ang)
+    if mvs_out:
+        n = int(out["nPoints"])
+        sc.vertices = out["points"].reshape(n, 3)
+        sc.vertex_view_start = np.asarray(out["viewStart"], np.int64)
+        vv = np.zeros(len(out["views"]), mvsi.VIEW_DTYPE)
+        vv["image_id"] = out["views"]; vv["confidence"] = out["weights"]
+        sc.vertex_views = vv
+        sc.vertices_normal = np.zeros((0, 3), np.float32) if out["normals"] is None else out["normals"].reshape(n, 3)
+        sc.vertices_color = np.zeros((0, 3), np.uint8) if out["colors"] is None else out["colors"].reshape(n, 3)
+        mvsi.save(mvs_out, sc)
+    return out
+
+
 def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None,
-                         crop_to_roi: bool = False, border_roi: float = 0.0, **load_args):
+                         crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, **load_args):
     """`Scene::DenseReconstruction(nFusionMode)` (libs/MVS/SceneDensify.cpp:1655-1750) for the PatchMatch path on one engine: prepare the views (`load_scene`), estimate all
     depth maps with the geometric rounds and the filters the option table asks for (`compute_depth_maps`; with `dmap_dir` under the reference's file contract), and -- unless
     `fusion_mode` is 1, "export depth maps only" -- fuse them and write `<scene>_dense.mvs` to `mvs_out`.  `opt`: an `optdense.OptDense` (default: the table's defaults with the
     application's own `--number-views 8`, `--estimate-normals 2`, `--number-views-fuse` left at the table's 2); `load_args` go to `load_scene` (image_loader,
     view_neighbors_file, ignore_mask_label, mask_path, mask_loader).  The SGM modes (-1, -2) are openmvs_amd.sgm_pipeline's.  After the fusion the cloud is finished
     (`finish_point_cloud`): `crop_to_roi` / `border_roi` as the application's `--crop-to-roi` (default 1 there, off here) / `--border-roi`, colours and normals of modes 1.
+    `filter_point_cloud` < 0: `Scene::PointCloudFilter` with that threshold on the finished cloud (`PatchMatchHIP.scene_cloud_filter`; default 0: off).
     Returns (SceneViews, cloud or None)."""
     from . import optdense
+    th_filter = int(filter_point_cloud)
     if fusion_mode not in (0, 1):
         raise ValueError("fusion_mode %d: the PatchMatch path is modes 0 (estimate + fuse) and 1 (depth maps only)" % fusion_mode)
     if opt is None:
@@ -499,6 +542,11 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     cloud = fuse_depth_maps(engine, sv, opt, bgr=sv.bgr)
     from . import mvsi
     cloud = finish_point_cloud(engine, (sv, mvsi.load(mvs_in) if crop_to_roi else None), opt, crop_to_roi, border_roi, cloud=cloud)
+    if th_filter < 0 and cloud["nPoints"]:
+        # the cones of the archive's images at their own resolution, as the application's Scene::Load leaves them; aliases of rescaled views are never listed
+        C, ang = archive_cones(mvsi.load(mvs_in))
+        extra = {k: cloud[k] for k in ("nDepths", "rounds") if k in cloud}
+        cloud = dict(engine.scene_cloud_filter(th_remove=th_filter, cam_C=C, cam_angle=ang), **extra)
     if mvs_out:
         save_dense_scene(mvs_in, mvs_out, cloud, sv)
     return sv, cloud

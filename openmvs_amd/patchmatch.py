@@ -56,6 +56,11 @@ class PMHipCloudParams(C.Structure):
                 ("bEstimateColor", C.c_int32), ("bEstimateNormal", C.c_int32), ("nNeighbors", C.c_int32)]
 
 
+class PMHipCloudFilterParams(C.Structure):
+    _fields_ = [("bVisibility", C.c_int32), ("thRemove", C.c_int32), ("nMinViews", C.c_uint32), ("nCams", C.c_int32),
+                ("camC", C.POINTER(C.c_double)), ("camAngle", C.POINTER(C.c_float))]
+
+
 PMHIP_ABI_VERSION = 7      # include/pmhip.h
 
 
@@ -63,7 +68,7 @@ class PMHipTuning(C.Structure):
     _fields_ = [("viewGroups", C.c_int32), ("wideMaxViews", C.c_int32), ("wideHyps", C.c_int32), ("sweepLanes", C.c_int32), ("quadBuffer", C.c_int32), ("widePixels", C.c_int32), ("wide8Pixels", C.c_int32), ("reserved0", C.c_int32)]
 
 
-EXPORTS = ["pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_scene_cloud_finish", "pmhip_scene_cloud_set", "pmhip_scene_cloud_knn", "pmhip_scene_cloud_times", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
+EXPORTS = ["pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_scene_cloud_finish", "pmhip_scene_cloud_set", "pmhip_scene_cloud_knn", "pmhip_scene_cloud_times", "pmhip_scene_cloud_load", "pmhip_scene_cloud_filter", "pmhip_scene_cloud_visibility", "pmhip_scene_cloud_filter_cones", "pmhip_scene_cloud_filter_times", "pmhip_scene_cloud_filter_counts", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
            "pmhip_estimate_depth_map", "pmhip_estimate_depth_map_masked", "pmhip_last_error", "pmhip_scene_create", "pmhip_scene_set_view",
            "pmhip_scene_estimate", "pmhip_scene_commit_round", "pmhip_scene_reset_view", "pmhip_scene_set_maps",
            "pmhip_scene_get_maps", "pmhip_scene_device_ptr", "pmhip_scene_copy", "pmhip_scene_filter", "pmhip_scene_filter_commit", "pmhip_scene_gap_interpolation", "pmhip_scene_remove_small_segments", "pmhip_scene_images_updated", "pmhip_scene_maps_updated", "pmhip_scene_bytes", "pmhip_sync",
@@ -396,6 +401,67 @@ class PatchMatchHIP:
             raise ValueError("viewStart must have nPoints + 1 entries")
         self._chk(self._lib.pmhip_scene_cloud_set(self._h, _fp(pts), vs.ctypes.data_as(C.POINTER(C.c_uint32)), vv.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                   None if w is None else _fp(w), C.c_uint64(len(pts))))
+
+    def scene_cloud_load(self, points, viewStart, views, weights=None, colors=None, normals=None, n_cams=0):
+        """Replace the resident cloud, colours (BGR bytes) and normals included when given (pmhip_scene_cloud_load).  `n_cams` > 0: the number of cameras the
+        view indices refer to, for an engine that holds no scene (an archive's cloud); 0: the loaded scene's images."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        vs = np.ascontiguousarray(viewStart, np.uint32); vv = np.ascontiguousarray(views, np.uint32)
+        if len(vs) != len(pts) + 1:
+            raise ValueError("viewStart must have nPoints + 1 entries")
+        w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+        col = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if (w is not None and len(w) != len(vv)) or (col is not None and len(col) != len(pts)) or (nrm is not None and len(nrm) != len(pts)):
+            raise ValueError("weights go with the views, colours and normals with the points")
+        self._chk(self._lib.pmhip_scene_cloud_load(self._h, _fp(pts), vs.ctypes.data_as(C.POINTER(C.c_uint32)), vv.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                   None if w is None else _fp(w), None if col is None else col.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   None if nrm is None else _fp(nrm), C.c_uint64(len(pts)), C.c_int32(int(n_cams))))
+
+    def scene_cloud_filter(self, th_remove=None, min_views=0, cam_C=None, cam_angle=None):
+        """Scene::PointCloudFilter(th_remove) (--filter-point-cloud) on the resident cloud, after PointCloud::RemoveMinViews(min_views) when `min_views` > 0
+        (pmhip_scene_cloud_filter); `th_remove` None: no visibility filter.  `cam_C` (n, 3) / `cam_angle` (n,): the camera centres and cone half-angles in
+        radians (FOV / width) -- both or neither; without them the loaded scene's cameras.  Returns scene_cloud_get() plus `visibility` (int32 per point of the
+        cloud the vote ran on, None without one), `cones` ((n, 2): angle, cosAngleSq as used, or None), `times` in ms (binning, cones, removal) and the
+        diagnostics `n_cones` / `n_candidates` (cones formed, candidates classified)."""
+        prm = PMHipCloudFilterParams()
+        prm.bVisibility = 0 if th_remove is None else 1
+        prm.thRemove = 0 if th_remove is None else int(th_remove)
+        prm.nMinViews = int(min_views)
+        if (cam_C is None) != (cam_angle is None):
+            raise ValueError("cam_C and cam_angle go together")
+        keep = None
+        if cam_C is not None:
+            cc = np.ascontiguousarray(cam_C, np.float64).reshape(-1, 3); ca = np.ascontiguousarray(cam_angle, np.float32).ravel()
+            if len(cc) != len(ca):
+                raise ValueError("cam_C and cam_angle must have one entry per camera")
+            keep = (cc, ca)
+            prm.nCams = len(ca); prm.camC = cc.ctypes.data_as(C.POINTER(C.c_double)); prm.camAngle = _fp(ca)
+        n_cams = prm.nCams if cam_C is not None else getattr(self, "_scene", (0,))[0]
+        # two calls when both are asked for: the size of the cloud between them is the size of `visibility`
+        before = C.c_uint64(); t = (C.c_double * 3)(); t_min = 0.0
+        if prm.nMinViews and prm.bVisibility:
+            only = PMHipCloudFilterParams(); only.nMinViews = prm.nMinViews
+            self._chk(self._lib.pmhip_scene_cloud_filter(self._h, C.byref(only), None, None))
+            self._chk(self._lib.pmhip_scene_cloud_filter_times(self._h, t))
+            t_min = t[2]; prm.nMinViews = 0
+        self._chk(self._lib.pmhip_scene_cloud_finish(self._h, C.byref(PMHipCloudParams()), C.byref(before), None))
+        self._chk(self._lib.pmhip_scene_cloud_filter(self._h, C.byref(prm), None, None))
+        del keep
+        out = self.scene_cloud_get()
+        self._chk(self._lib.pmhip_scene_cloud_filter_times(self._h, t))
+        out["times"] = dict(binning=t[0], cones=t[1], removal=t[2] + t_min)
+        cnt = (C.c_uint64 * 2)()
+        self._chk(self._lib.pmhip_scene_cloud_filter_counts(self._h, cnt))
+        out["n_cones"], out["n_candidates"] = int(cnt[0]), int(cnt[1])
+        out["visibility"] = None; out["cones"] = None
+        if th_remove is not None and int(before.value) > 0:
+            cones = np.zeros((n_cams, 2), np.float32)
+            self._chk(self._lib.pmhip_scene_cloud_filter_cones(self._h, _fp(cones)))
+            vis = np.zeros(int(before.value), np.int32)
+            self._chk(self._lib.pmhip_scene_cloud_visibility(self._h, vis.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(len(vis))))
+            out["cones"] = cones; out["visibility"] = vis
+        return out
 
     def scene_cloud_knn(self, queries, k=16):
         """The k nearest points of the resident cloud for each query index, nearest first (pmhip_scene_cloud_knn): (nq, k) uint32."""

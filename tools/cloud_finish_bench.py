@@ -2,7 +2,9 @@
 9 x 1920x1080, cropped to a box that keeps ~90 %, coloured and given PCA normals (k = 16).  Prints the engine's step times (crop, grid build,
 k-NN + PCA, colours; each ended by a stream synchronisation, no download), points per second, and the same-box CPU yardstick: scipy's
 cKDTree(...).query(k=16, workers=16) plus the numpy PCA over the same neighbour sets.  One JSON line per cloud at the end.
-    python tools/cloud_finish_bench.py [--reps 3] [--no-cpu] [--only 4k|1080p]
+    python tools/cloud_finish_bench.py [--reps 3] [--no-cpu] [--only 4k|1080p] [--filter TH]
+--filter TH adds Scene::PointCloudFilter(TH) (pmhip_scene_cloud_filter, csrc/pm_cloud_filter.hip) on the finished cloud: its step times (binning, cone pass,
+removal), the cones, the candidates classified per cone and the fusion's own wall time next to it.
 Kernel figures: run it under `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/cloud_finish_bench.py --no-cpu`."""
 import argparse
 import json
@@ -21,6 +23,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--no-cpu", action="store_true")
 ap.add_argument("--only", default="")
+ap.add_argument("--filter", type=int, default=None, metavar="TH")
 a = ap.parse_args()
 
 CASES = [("4k", 5, 3840, 2160, 4), ("1080p", 9, 1920, 1080, 8)]
@@ -81,6 +84,27 @@ for name, V, W, H, nsrc in CASES:
         res["cpu_yardstick_s"] = {k: round(v, 3) for k, v in y.items()}
         res["speedup_normals_vs_cpu"] = round(y["total_s"] * 1e3 / res["normals_ms"], 1)
         print("  CPU yardstick (cKDTree workers=16 + numpy PCA): %s s" % res["cpu_yardstick_s"], flush=True)
+    if a.filter is not None:
+        fbest = None
+        for r in range(a.reps + 1):
+            t0 = time.time()
+            e.scene_fuse(order, bEstimateColor=False, bEstimateNormal=False)
+            fuse_ms = (time.time() - t0) * 1e3                   # (with the download of the fused cloud)
+            e.scene_cloud_finish(crop_obb=obb, estimate_colors=True, estimate_normals=True)
+            t0 = time.time()
+            out = e.scene_cloud_filter(th_remove=a.filter)
+            wall = time.time() - t0
+            tm = out["times"]
+            print("  filter run %d: %s ms, %d -> %d points, %d cones, %.0f candidates per cone, wall incl. download %.1f ms (fusion %.1f ms)" %
+                  (r, {k: round(v, 2) for k, v in tm.items()}, len(out["visibility"]), out["nPoints"], out["n_cones"], out["n_candidates"] / max(out["n_cones"], 1), wall * 1e3, fuse_ms), flush=True)
+            if r and (fbest is None or sum(tm.values()) < sum(fbest[0].values())):
+                fbest = (dict(tm), fuse_ms)
+        tm, fuse_ms = fbest
+        vis = out["visibility"]
+        res["filter"] = dict(th=a.filter, ms={k: round(v, 2) for k, v in tm.items()}, total_ms=round(sum(tm.values()), 2), points=int(len(vis)), kept=int(out["nPoints"]),
+                             cones=out["n_cones"], candidates=out["n_candidates"], candidates_per_cone=round(out["n_candidates"] / max(out["n_cones"], 1), 1),
+                             ns_per_cone=round(tm["cones"] * 1e6 / max(out["n_cones"], 1), 2), ps_per_classification=round(tm["cones"] * 1e9 / max(out["n_candidates"], 1), 2),
+                             nonzero=int((vis != 0).sum()), fuse_wall_ms=round(fuse_ms, 1))
     results.append(res)
     e.close()
 for r in results:
