@@ -4,6 +4,7 @@
 #include "sgm_kernels_sub.hip"
 #include "sgm_post.hip"
 #include "sgm_tsgm.hip"
+#include "hip_buf.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -12,26 +13,26 @@
 
 #define SGMCHK(e, call) do { hipError_t _r = (call); if (_r != hipSuccess) { (e)->err = std::string(#call) + ": " + hipGetErrorString(_r); return SGMHIP_E_HIP; } } while (0)
 
-struct sgmhip_engine {
+struct SGMProblemBufs {   // buffers of the resident problem and what they hold: grown together, never shrunk (sgmReserve)
+	size_t capImg = 0, capPix = 0, capCosts = 0;
+	DevBuf<unsigned char> d_color; DevBuf<float> d_grayL, d_grayR;
+	DevBuf<SGMPixel> d_pixels; DevBuf<unsigned char> d_costs; DevBuf<unsigned short> d_accums; DevBuf<float4> d_setup;
+	DevBuf<short> d_disp; DevBuf<unsigned short> d_cost;
+};
+struct sgmhip_engine : SGMProblemBufs {
 	int device = 0; hipStream_t stream = nullptr; std::string err;
 	int w = 0, h = 0, vw = 0, vh = 0, maxNumDisp = 0; uint64_t numCosts = 0;
-	size_t capImg = 0, capPix = 0, capCosts = 0;
-	unsigned char* d_color = nullptr; float* d_grayL = nullptr; float* d_grayR = nullptr;
-	SGMPixel* d_pixels = nullptr; unsigned char* d_costs = nullptr; unsigned short* d_accums = nullptr; float4* d_setup = nullptr;
-	short* d_disp = nullptr; unsigned short* d_cost = nullptr; unsigned short* d_P2s = nullptr;
+	DevBuf<unsigned short> d_P2s;
 	bool statsOn = false; SGMHipStats stats{};
-	unsigned char* d_deltas = nullptr; size_t capDeltas = 0; int maxP2 = 65535;   // DELTA aggregation (uniform ranges, max P2 <= 255): 8 byte volumes instead of atomic u16 sums
-	bool uniform = false; int uniformMin = 0, uniformMax = 0; SGMUniform* d_uniform = nullptr;   // every pixel has [uniformMin, uniformMax) and idx = pixel * nD (checked on the device at set_problem): the register-resident path kernel applies
+	DevBuf<unsigned char> d_deltas; size_t capDeltas = 0; int maxP2 = 65535;   // DELTA aggregation (uniform ranges, max P2 <= 255): 8 byte volumes instead of atomic u16 sums
+	bool uniform = false; int uniformMin = 0, uniformMax = 0; DevBuf<SGMUniform> d_uniform;   // every pixel has [uniformMin, uniformMax) and idx = pixel * nD (checked on the device at set_problem): the register-resident path kernel applies
 	int subGroups = 0;            // 0, or the lanes per sub-group (8, 16, 32): Match with the sub-group kernels of sgm_kernels_sub.hip (narrow, ragged ranges); see sgmhip_set_sub_group_kernels
 	struct Ev { hipEvent_t a, b; int kind; }; std::vector<Ev> events;
 };
 
 static void sgmFree(sgmhip_engine* e) {
 	hipSetDevice(e->device);
-	void* ps[] = {e->d_color, e->d_grayL, e->d_grayR, e->d_pixels, e->d_costs, e->d_accums, e->d_disp, e->d_cost, e->d_setup};
-	for (void* p : ps) if (p) hipFree(p);
-	e->d_color = nullptr; e->d_grayL = e->d_grayR = nullptr; e->d_pixels = nullptr; e->d_costs = nullptr; e->d_accums = nullptr; e->d_disp = nullptr; e->d_cost = nullptr; e->d_setup = nullptr;
-	e->capImg = e->capPix = e->capCosts = 0;
+	static_cast<SGMProblemBufs&>(*e) = SGMProblemBufs{};
 }
 static void evB(sgmhip_engine* e, int kind) { if (!e->statsOn) return; sgmhip_engine::Ev ev; ev.kind = kind; hipEventCreate(&ev.a); hipEventCreate(&ev.b); hipEventRecord(ev.a, e->stream); e->events.push_back(ev); }
 static void evE(sgmhip_engine* e) { if (!e->statsOn) return; hipEventRecord(e->events.back().b, e->stream); }
@@ -50,9 +51,9 @@ static int sgmReserve(sgmhip_engine* e, int w, int h, uint64_t numCosts, int max
 		SGMCHK(e, hipStreamSynchronize(e->stream));
 		const size_t cI = std::max(nImg, e->capImg), cP = std::max(nPix, e->capPix), cC = std::max<size_t>(numCosts, e->capCosts);
 		sgmFree(e);
-		SGMCHK(e, hipMalloc(&e->d_color, cI * 3)); SGMCHK(e, hipMalloc(&e->d_grayL, cI * 4)); SGMCHK(e, hipMalloc(&e->d_grayR, cI * 4));
-		SGMCHK(e, hipMalloc(&e->d_pixels, cP * sizeof(SGMPixel))); SGMCHK(e, hipMalloc(&e->d_disp, cP * 2)); SGMCHK(e, hipMalloc(&e->d_cost, cP * 2)); SGMCHK(e, hipMalloc(&e->d_setup, cP * sizeof(float4)));
-		SGMCHK(e, hipMalloc(&e->d_costs, cC + 256)); SGMCHK(e, hipMalloc(&e->d_accums, (cC + 3) / 4 * 8 + 8)); // u16 sums, addressed as 32-bit words by the path kernels
+		SGMCHK(e, e->d_color.alloc(cI * 3)); SGMCHK(e, e->d_grayL.alloc(cI)); SGMCHK(e, e->d_grayR.alloc(cI));
+		SGMCHK(e, e->d_pixels.alloc(cP)); SGMCHK(e, e->d_disp.alloc(cP)); SGMCHK(e, e->d_cost.alloc(cP)); SGMCHK(e, e->d_setup.alloc(cP));
+		SGMCHK(e, e->d_costs.alloc(cC + 256)); SGMCHK(e, e->d_accums.alloc((cC + 3) / 4 * 4 + 4)); // u16 sums, addressed as 32-bit words by the path kernels
 		e->capImg = cI; e->capPix = cP; e->capCosts = cC;
 	}
 	e->w = w; e->h = h; e->vw = w - 2 * SGM_HW; e->vh = h - 2 * SGM_HW; e->numCosts = numCosts; e->maxNumDisp = maxNumDisp;
@@ -69,7 +70,7 @@ int sgmhip_create(int device, sgmhip_engine** out) {
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device >= n) return SGMHIP_E_NODEVICE;
 	if (device < 0) device = 0;
 	sgmhip_engine* e = new sgmhip_engine(); e->device = device;
-	if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&e->d_P2s, 512) != hipSuccess) { delete e; return SGMHIP_E_HIP; }
+	if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess || e->d_P2s.alloc(256) != hipSuccess) { delete e; return SGMHIP_E_HIP; }
 	*out = e;
 	return 0;
 }
@@ -77,7 +78,7 @@ void sgmhip_destroy(sgmhip_engine* e) {
 	if (!e) return;
 	hipSetDevice(e->device); hipStreamSynchronize(e->stream);
 	for (auto& ev : e->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
-	sgmFree(e); if (e->d_P2s) hipFree(e->d_P2s); if (e->d_uniform) hipFree(e->d_uniform); if (e->d_deltas) hipFree(e->d_deltas);
+	sgmFree(e); e->d_P2s.release(); e->d_uniform.release(); e->d_deltas.release();
 	hipStreamDestroy(e->stream); delete e;
 }
 const char* sgmhip_last_error(sgmhip_engine* e) { return e ? e->err.c_str() : "null engine"; }
@@ -102,7 +103,7 @@ int sgmhip_set_problem(sgmhip_engine* e, const uint8_t* leftBGR, const float* le
 	static const bool allowUniform = [] { const char* v = getenv("SGMHIP_UNIFORM"); return !v || atoi(v) != 0; }();
 	SGMUniform hu = {1, 0, 0, 0};
 	if (allowUniform) {
-		if (!e->d_uniform) SGMCHK(e, hipMalloc(&e->d_uniform, sizeof(SGMUniform)));
+		if (!e->d_uniform) SGMCHK(e, e->d_uniform.alloc(1));
 		SGMCHK(e, hipMemcpyAsync(e->d_uniform, &hu, sizeof(hu), hipMemcpyHostToDevice, e->stream));
 		hipLaunchKernelGGL(sgm_uniform_check_kernel, dim3((unsigned)((nPix + 255) / 256)), dim3(256), 0, e->stream, e->d_pixels, (long)nPix, e->d_uniform);
 		SGMCHK(e, hipMemcpyAsync(&hu, e->d_uniform, sizeof(hu), hipMemcpyDeviceToHost, e->stream));
@@ -114,7 +115,7 @@ int sgmhip_set_problem(sgmhip_engine* e, const uint8_t* leftBGR, const float* le
 }
 
 static void launchPath(sgmhip_engine* e, hipStream_t st, int NK, int lines, int P1, const SGMDirs& dirs, bool delta) {
-#define SGM_LAUNCH_PATH(NK_, DL_) hipLaunchKernelGGL((sgm_path_kernel<NK_, DL_>), dim3(lines), dim3(64), 0, st, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, e->d_costs, (unsigned*)e->d_accums, e->d_P2s, P1, dirs, e->d_deltas, (unsigned long long)e->numCosts)
+#define SGM_LAUNCH_PATH(NK_, DL_) hipLaunchKernelGGL((sgm_path_kernel<NK_, DL_>), dim3(lines), dim3(64), 0, st, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, P1, dirs, e->d_deltas, (unsigned long long)e->numCosts)
 	switch (NK) {
 	case 1: if (delta) SGM_LAUNCH_PATH(1, true); else SGM_LAUNCH_PATH(1, false); break;
 	case 2: if (delta) SGM_LAUNCH_PATH(2, true); else SGM_LAUNCH_PATH(2, false); break;
@@ -126,8 +127,8 @@ static void launchPath(sgmhip_engine* e, hipStream_t st, int NK, int lines, int 
 static bool ensureDeltas(sgmhip_engine* e) {
 	if (e->capDeltas >= e->numCosts * 8) return true;
 	if (hipStreamSynchronize(e->stream) != hipSuccess) return false;
-	if (e->d_deltas) { hipFree(e->d_deltas); e->d_deltas = nullptr; e->capDeltas = 0; }
-	if (hipMalloc(&e->d_deltas, e->numCosts * 8 + 16) == hipSuccess) { e->capDeltas = e->numCosts * 8; return true; }
+	e->capDeltas = 0;
+	if (e->d_deltas.alloc(e->numCosts * 8 + 16) == hipSuccess) { e->capDeltas = e->numCosts * 8; return true; }
 	(void)hipGetLastError();
 	return false;
 }
@@ -188,7 +189,7 @@ static int sgmMatchSubT(sgmhip_engine* e, uint16_t P1) {
 	sd.first[8] = total;
 	evB(e, 1);
 	if (total > 0) {
-#define SGM_LAUNCH_SUB(MD_, DL_) hipLaunchKernelGGL((sgm_path_sub_kernel<LP, MD_, DL_>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, e->d_costs, (unsigned*)e->d_accums, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
+#define SGM_LAUNCH_SUB(MD_, DL_) hipLaunchKernelGGL((sgm_path_sub_kernel<LP, MD_, DL_>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
 		if (e->maxNumDisp <= 64) { if (delta) SGM_LAUNCH_SUB(64, true); else SGM_LAUNCH_SUB(64, false); }
 		else { if (delta) SGM_LAUNCH_SUB(256, true); else SGM_LAUNCH_SUB(256, false); }
 #undef SGM_LAUNCH_SUB
@@ -269,10 +270,10 @@ static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
 	if (total > 0) {
 		if (e->uniform && NK <= 2) {
 			const int align = e->maxNumDisp % 2 == 0 ? 2 : 1;
-#define SGM_LAUNCH_UNIFORM(NK_, AL_, DL_) hipLaunchKernelGGL((sgm_path_uniform_kernel<NK_, AL_, DL_, false>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->maxNumDisp, e->d_costs, (unsigned*)e->d_accums, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
+#define SGM_LAUNCH_UNIFORM(NK_, AL_, DL_) hipLaunchKernelGGL((sgm_path_uniform_kernel<NK_, AL_, DL_, false>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->maxNumDisp, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
 			static const int stageMaxNK = [] { const char* v = getenv("SGMHIP_STAGE"); return v ? atoi(v) : 2; }();   // stage the delta bytes for up to this many entries per lane (0: never)
 			if (delta && e->maxNumDisp % 16 == 0 && NK <= stageMaxNK) {   // delta bytes staged through LDS, written out 16 bytes at a time
-#define SGM_LAUNCH_STAGED(NK_) hipLaunchKernelGGL((sgm_path_uniform_kernel<NK_, 2, true, true>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->maxNumDisp, e->d_costs, (unsigned*)e->d_accums, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
+#define SGM_LAUNCH_STAGED(NK_) hipLaunchKernelGGL((sgm_path_uniform_kernel<NK_, 2, true, true>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->maxNumDisp, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
 				if (NK == 1) SGM_LAUNCH_STAGED(1); else SGM_LAUNCH_STAGED(2);
 #undef SGM_LAUNCH_STAGED
 			} else if (delta) {
@@ -328,18 +329,14 @@ int sgmhip_stats_get(sgmhip_engine* e, SGMHipStats* out) { if (!e || !out) retur
 
 // ---- tSGM steps around Match (SemiGlobalMatcher.cpp:1449-1811), see csrc/sgm_post.h ---------------------------------------------
 namespace {
-struct DevBuf {   // scoped device allocation for the stateless helpers
-	void* p = nullptr;
-	~DevBuf() { if (p) hipFree(p); }
-	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
+using Scoped = DevBuf<unsigned char>;   // scoped device allocation (bytes) for the stateless helpers
 inline unsigned gridFor(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 65535); }
 }
 
 int sgmhip_consistency_cross_check(sgmhip_engine* e, int16_t* l2r, const int16_t* r2l, int wl, int h, int wr, int thCross) {
 	if (!e || !l2r || !r2l || wl <= 0 || wr <= 0 || h <= 0 || thCross < 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, b; const size_t nl = (size_t)wl * h, nr = (size_t)wr * h;
+	Scoped a, b; const size_t nl = (size_t)wl * h, nr = (size_t)wr * h;
 	SGMCHK(e, a.alloc(nl * 2)); SGMCHK(e, b.alloc(nr * 2));
 	SGMCHK(e, hipMemcpyAsync(a.p, l2r, nl * 2, hipMemcpyHostToDevice, e->stream)); SGMCHK(e, hipMemcpyAsync(b.p, r2l, nr * 2, hipMemcpyHostToDevice, e->stream));
 	hipLaunchKernelGGL(sgmp_cross_check_kernel, dim3(gridFor(nl)), dim3(256), 0, e->stream, (int16_t*)a.p, (const int16_t*)b.p, wl, wr, h, thCross);
@@ -351,7 +348,7 @@ int sgmhip_consistency_cross_check(sgmhip_engine* e, int16_t* l2r, const int16_t
 int sgmhip_filter_by_cost(sgmhip_engine* e, int16_t* disparity, const uint16_t* cost, int w, int h, uint16_t th) {
 	if (!e || !disparity || !cost || w <= 0 || h <= 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, b; const size_t n = (size_t)w * h;
+	Scoped a, b; const size_t n = (size_t)w * h;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, b.alloc(n * 2));
 	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream)); SGMCHK(e, hipMemcpyAsync(b.p, cost, n * 2, hipMemcpyHostToDevice, e->stream));
 	hipLaunchKernelGGL(sgmp_filter_by_cost_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (int16_t*)a.p, (const uint16_t*)b.p, n, th);
@@ -363,7 +360,7 @@ int sgmhip_filter_by_cost(sgmhip_engine* e, int16_t* disparity, const uint16_t* 
 int sgmhip_extract_mask(sgmhip_engine* e, const int16_t* disparity, uint8_t* mask, int w, int h, int thValid, int initValid) {
 	if (!e || !disparity || !mask || w <= 0 || h <= 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, b; const size_t n = (size_t)w * h;
+	Scoped a, b; const size_t n = (size_t)w * h;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, b.alloc(n));
 	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
 	if (initValid) SGMCHK(e, hipMemsetAsync(b.p, 0xFF, n, e->stream));      // maskMap.create(size); setTo(VALID), :1521-1524
@@ -377,7 +374,7 @@ int sgmhip_extract_mask(sgmhip_engine* e, const int16_t* disparity, uint8_t* mas
 int sgmhip_upscale_mask(sgmhip_engine* e, const uint8_t* mask, int w, int h, uint8_t* mask2x, int w2, int h2) {
 	if (!e || !mask || !mask2x || w <= 0 || h <= 0 || w2 <= 0 || h2 <= 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, b; const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
+	Scoped a, b; const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
 	SGMCHK(e, a.alloc(n)); SGMCHK(e, b.alloc(n2));
 	SGMCHK(e, hipMemcpyAsync(a.p, mask, n, hipMemcpyHostToDevice, e->stream));
 	hipLaunchKernelGGL(sgmp_upscale_mask_kernel, dim3(gridFor(n2)), dim3(256), 0, e->stream, (const uint8_t*)a.p, w, h, (uint8_t*)b.p, w2, h2);
@@ -389,7 +386,7 @@ int sgmhip_upscale_mask(sgmhip_engine* e, const uint8_t* mask, int w, int h, uin
 int sgmhip_flip_direction(sgmhip_engine* e, const int16_t* l2r, int w, int h, int16_t* r2l) {
 	if (!e || !l2r || !r2l || w <= 0 || h <= 0 || w > 65534) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, k, b; const size_t n = (size_t)w * h;
+	Scoped a, k, b; const size_t n = (size_t)w * h;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, k.alloc(n * 4)); SGMCHK(e, b.alloc(n * 2));
 	SGMCHK(e, hipMemcpyAsync(a.p, l2r, n * 2, hipMemcpyHostToDevice, e->stream));
 	SGMCHK(e, hipMemsetAsync(k.p, 0, n * 4, e->stream));
@@ -415,7 +412,7 @@ int sgmhip_disparity2range_map(sgmhip_engine* e, const int16_t* disparity, int w
 		int minNumDisp, int minNumDispInvalid, SGMHipPixelData* pixels, uint64_t* numCosts, int* maxNumDisp) {
 	if (!e || !disparity || !mask2x || !pixels || w <= 0 || h <= 0 || w2 <= SGM_HW + 2 * w || h2 < SGM_HW + 2 * h) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, m, r; const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
+	Scoped a, m, r; const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, m.alloc(n2)); SGMCHK(e, r.alloc(n * 4));
 	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream)); SGMCHK(e, hipMemcpyAsync(m.p, mask2x, n2, hipMemcpyHostToDevice, e->stream));
 	hipLaunchKernelGGL(sgmp_range_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (const int16_t*)a.p, w, h, (const uint8_t*)m.p, w2, minNumDisp, minNumDispInvalid, (short2*)r.p);
@@ -446,7 +443,7 @@ int sgmhip_depth2disparity_map(sgmhip_engine* e, const float* depthMap, int dw, 
 		int16_t* disparity, int w, int h) {
 	if (!e || !depthMap || !invH || !invQ || !disparity || dw <= 0 || dh <= 0 || w <= 0 || h <= 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, b; const size_t nd = (size_t)dw * dh, n = (size_t)w * h;
+	Scoped a, b; const size_t nd = (size_t)dw * dh, n = (size_t)w * h;
 	SGMCHK(e, a.alloc(nd * 4)); SGMCHK(e, b.alloc(n * 2));
 	SGMCHK(e, hipMemcpyAsync(a.p, depthMap, nd * 4, hipMemcpyHostToDevice, e->stream));
 	SGMPMat mh{}, mq{}; memcpy(mh.m, invH, 72); memcpy(mq.m, invQ, 128);
@@ -460,7 +457,7 @@ int sgmhip_disparity2depth_map(sgmhip_engine* e, const int16_t* disparity, const
 		int subpixelSteps, float* depthMap, float* confMap, int dw, int dh) {
 	if (!e || !disparity || !H || !Q || !depthMap || (cost && !confMap) || dw <= 0 || dh <= 0 || w <= 0 || h <= 0 || subpixelSteps <= 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, c, d, f; const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
+	Scoped a, c, d, f; const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, c.alloc(n * 2)); SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, f.alloc(nd * 4));
 	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
 	if (cost) SGMCHK(e, hipMemcpyAsync(c.p, cost, n * 2, hipMemcpyHostToDevice, e->stream));
@@ -476,7 +473,7 @@ int sgmhip_project_disparity2depth_map(sgmhip_engine* e, const int16_t* disparit
 		float* depthMap, float* depthRangeMap, float* confMap, int dw, int dh, int* anyDepth) {
 	if (!e || !disparity || !Q || !depthMap || !depthRangeMap || (cost && !confMap) || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || subpixelSteps <= 0 || (size_t)w * h > 0xFFFFFFFFull) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, c, k, d, rg, cf, cnt; const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
+	Scoped a, c, k, d, rg, cf, cnt; const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, c.alloc(n * 2)); SGMCHK(e, k.alloc(nd * 4 * 8)); SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, rg.alloc(nd * 8)); SGMCHK(e, cf.alloc(nd * 4)); SGMCHK(e, cnt.alloc(4));
 	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
 	if (cost) SGMCHK(e, hipMemcpyAsync(c.p, cost, n * 2, hipMemcpyHostToDevice, e->stream));
@@ -502,7 +499,7 @@ int sgmhip_fuse_pairs(sgmhip_engine* e, const float* const* depthMaps, const flo
 	if (!e || !depthMaps || !depthRangeMaps || !confMaps || nPairs < 0 || nPairs > SGMP_MAX_PAIRS || dw <= 0 || dh <= 0 || !depthMap || !confMap) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
 	const size_t nd = (size_t)dw * dh;
-	std::vector<DevBuf> bufs((size_t)nPairs * 3);
+	std::vector<Scoped> bufs((size_t)nPairs * 3);
 	SGMPPairs pr{};
 	for (int p = 0; p < nPairs; ++p) {
 		if (!depthMaps[p] || !depthRangeMaps[p] || !confMaps[p]) return SGMHIP_E_ARG;
@@ -512,7 +509,7 @@ int sgmhip_fuse_pairs(sgmhip_engine* e, const float* const* depthMaps, const flo
 		SGMCHK(e, hipMemcpyAsync(bufs[p * 3 + 2].p, confMaps[p], nd * 4, hipMemcpyHostToDevice, e->stream));
 		pr.depth[p] = (const float*)bufs[p * 3].p; pr.range[p] = (const float*)bufs[p * 3 + 1].p; pr.conf[p] = (const float*)bufs[p * 3 + 2].p;
 	}
-	DevBuf d, c; SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, c.alloc(nd * 4));
+	Scoped d, c; SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, c.alloc(nd * 4));
 	hipLaunchKernelGGL(sgmp_fuse_pairs_kernel, dim3(gridFor(nd)), dim3(256), 0, e->stream, pr, nPairs, nd, minViews, (float*)d.p, (float*)c.p);
 	SGMCHK(e, hipMemcpyAsync(depthMap, d.p, nd * 4, hipMemcpyDeviceToHost, e->stream));
 	SGMCHK(e, hipMemcpyAsync(confMap, c.p, nd * 4, hipMemcpyDeviceToHost, e->stream));
@@ -528,11 +525,11 @@ int sgmhip_fuse_disparities(sgmhip_engine* e, int nPairs, const int16_t* const* 
 	SGMCHK(e, hipSetDevice(e->device));
 	hipStream_t st = e->stream;
 	const size_t nd = (size_t)dw * dh;
-	std::vector<DevBuf> maps((size_t)nPairs * 3);
-	DevBuf k, cnt, d, c;
+	std::vector<Scoped> maps((size_t)nPairs * 3);
+	Scoped k, cnt, d, c;
 	SGMCHK(e, k.alloc(nd * 4 * 8)); SGMCHK(e, cnt.alloc(4 * (size_t)std::max(nPairs, 1))); SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, c.alloc(nd * 4));
 	SGMCHK(e, hipMemsetAsync(cnt.p, 0, 4 * (size_t)std::max(nPairs, 1), st));
-	std::vector<DevBuf> in((size_t)nPairs * 2);
+	std::vector<Scoped> in((size_t)nPairs * 2);
 	for (int p = 0; p < nPairs; ++p) {
 		const int w = widths[p], h = heights[p];
 		if (!disparities[p] || !costs[p] || w <= 0 || h <= 0 || subpixelSteps[p] <= 0 || (size_t)w * h > 0xFFFFFFFFull) return SGMHIP_E_ARG;
@@ -565,7 +562,7 @@ int sgmhip_fuse_disparities(sgmhip_engine* e, int nPairs, const int16_t* const* 
 int sgmhip_filter_speckles(sgmhip_engine* e, int16_t* disparity, int w, int h, int maxSpeckleSize, int maxDiff) {
 	if (!e || !disparity || w <= 0 || h <= 0 || maxSpeckleSize < 0 || maxDiff < 0 || (size_t)w * h > 0x7fffffffull) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	DevBuf a, p, z; const size_t n = (size_t)w * h;
+	Scoped a, p, z; const size_t n = (size_t)w * h;
 	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, p.alloc(n * 4)); SGMCHK(e, z.alloc(n * 4));
 	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
 	const unsigned g = gridFor(n);
@@ -611,7 +608,7 @@ int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* r
 	hipStream_t st = e->stream;
 	const size_t nFull = (size_t)w * h, nValid = (size_t)(w - 2 * SGM_HW) * (h - 2 * SGM_HW);
 	// full-resolution inputs and the per-level working set (sized for the finest level)
-	DevBuf fLB, fRB, fLG, fRG, fLM, fRM, lB, rB, lG, rG, lM, rM, lM2, rM2, lD, rD, lDn, rDn, keys, ranges, tiles, scal, par, siz;
+	Scoped fLB, fRB, fLG, fRG, fLM, fRM, lB, rB, lG, rG, lM, rM, lM2, rM2, lD, rD, lDn, rDn, keys, ranges, tiles, scal, par, siz;
 	SGMCHK(e, fLB.alloc(nFull * 3)); SGMCHK(e, fRB.alloc(nFull * 3)); SGMCHK(e, fLG.alloc(nFull * 4)); SGMCHK(e, fRG.alloc(nFull * 4)); SGMCHK(e, fLM.alloc(nFull)); SGMCHK(e, fRM.alloc(nFull));
 	SGMCHK(e, lB.alloc(nFull * 3)); SGMCHK(e, rB.alloc(nFull * 3)); SGMCHK(e, lG.alloc(nFull * 4)); SGMCHK(e, rG.alloc(nFull * 4));
 	SGMCHK(e, lM.alloc(nValid)); SGMCHK(e, rM.alloc(nValid)); SGMCHK(e, lM2.alloc(nValid)); SGMCHK(e, rM2.alloc(nValid));

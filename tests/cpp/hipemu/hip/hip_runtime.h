@@ -334,6 +334,7 @@ static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 namespace hipemu {
 enum { GUARD = 64 };
 inline std::map<void*, size_t>& allocs() { static std::map<void*, size_t> m; return m; }
+inline int64_t& fail_malloc_in() { static int64_t k = 0; return k; }   // > 0: that many hipMalloc calls from now, the last of them fails
 inline void check_guards(const char* when) {
 	for (auto& a : allocs()) {
 		const unsigned char* b = (const unsigned char*)a.first;
@@ -346,6 +347,7 @@ inline void check_guards(const char* when) {
 }
 }
 template <class T> static inline hipError_t hipMalloc(T** p, size_t n) {
+	if (hipemu::fail_malloc_in() > 0 && --hipemu::fail_malloc_in() == 0) { *p = nullptr; return hipErrorOutOfMemory; }   // (hipemu_fail_malloc_at, for the tests of the error paths)
 	char* q = (char*)malloc(n + 2 * hipemu::GUARD);
 	if (!q) return hipErrorOutOfMemory;
 	memset(q, 0xA5, hipemu::GUARD); memset(q + hipemu::GUARD, 0xCD, n); memset(q + hipemu::GUARD + n, 0xA5, hipemu::GUARD);
@@ -389,6 +391,14 @@ template <class... P, class... A> inline void launch_args(const char* name, dim3
 }
 }
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) hipemu::launch_args(#kernel, dim3(grid), dim3(block), kernel, ##__VA_ARGS__)
+
+// device memory for the tests (ctypes): allocations alive and their bytes; and a switch that makes the k-th hipMalloc from now return hipErrorOutOfMemory
+// (once; k < 1 turns it off).  Host code only: nothing on a device is made to fail.
+extern "C" __attribute__((weak, visibility("default"))) void hipemu_live_allocs(uint64_t out[2]) {
+	out[0] = hipemu::allocs().size(); out[1] = 0;
+	for (auto& a : hipemu::allocs()) out[1] += a.second;
+}
+extern "C" __attribute__((weak, visibility("default"))) void hipemu_fail_malloc_at(int64_t k) { hipemu::fail_malloc_in() = k > 0 ? k : 0; }
 
 // counters for the tests (ctypes): launches, fibers run, cross-lane exchanges resolved, reads of lanes that did not take part in an exchange
 extern "C" __attribute__((weak, visibility("default"))) void hipemu_counters(uint64_t out[4]) {
