@@ -122,6 +122,30 @@ int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* r
                       const uint8_t* leftMask, const uint8_t* rightMask, int w, int h, unsigned minResolution, const int16_t* initLeftDisparity,
                       int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels);
 
+/* ---- the resident scene of the SGM path: images uploaded once, pairs rectified on the device (csrc/sgm_rectify.hip) ----------------------------------
+ * Errors of these calls are SGMHIP_E_ARG with the reason in sgmhip_last_error; the engine stays usable. */
+/* A table of nImages image slots, all unset; replaces a scene the engine held. */
+int sgmhip_scene_create(sgmhip_engine* e, int nImages);
+/* Upload image idx (host pointer, BGR 8-bit, w x h, row-major); every image has its own size.  Setting a slot again replaces its image. */
+int sgmhip_scene_set_image(sgmhip_engine* e, int idx, const uint8_t* bgr, int w, int h);
+int sgmhip_scene_clear(sgmhip_engine* e);
+/* The pixel part of Image::StereoRectifyImages (libs/MVS/Image.cpp:296-322) and the toGray(bNormalize, bSRGB) of the rectified images
+ * (SemiGlobalMatcher.cpp:579-582) for both images of a pair in one launch: per pixel (x, y) of the w x h rectified image of a side, (X, Y) = invH (x, y, 1)
+ * dehomogenised in double; the BGR pixel is the float bilinear resample of the four taps around it (a tap outside the source counts as 0) rounded
+ * floor(v + 0.5) to 8 bits; the mask is 255 where 0 <= X <= W0 and 0 <= Y <= H0, else 0; gray = (0.114 T[B] + 0.587 T[G]) + 0.299 T[R] of the rounded pixel.
+ * Bit for bit openmvs_amd/rectify.py warp_perspective_u8 followed by sgm_pipeline.to_gray_linear.  invH1 / invH2: the inverses of the rectifying
+ * homographies (3x3 row-major doubles); srgb2lin: the sRGB -> linear table (g_ptrsRGB82RGBf, libs/Common/Types.inl:1595-1607), built by the host.
+ * w, h: the extent to produce -- cropping the rectified size at the right / bottom leaves the pixel coordinates as they are.  The three maps of both sides stay
+ * resident until the next call. */
+int sgmhip_rectify_pair(sgmhip_engine* e, int idxLeft, int idxRight, const double invH1[9], const double invH2[9], int w, int h, const float srgb2lin[256]);
+/* Download the resident rectified maps of a side (0 left, 1 right); any pointer may be NULL.  bgr w*h*3, gray w*h floats, mask w*h. */
+int sgmhip_rectified_get(sgmhip_engine* e, int side, uint8_t* bgr, float* gray, uint8_t* mask);
+/* sgmhip_tsgm_match on the resident rectified pair (its size must be a multiple of 2^levels): no image travels. */
+int sgmhip_tsgm_match_rectified(sgmhip_engine* e, unsigned minResolution, const int16_t* initLeftDisparity, int nSpeckleSize, int subpixelMode, int subpixelSteps,
+                                uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels);
+/* HIP-event time (ms) of the rectification kernel and its number of launches since the last sgmhip_stats_reset(e, 1); either pointer may be NULL. */
+int sgmhip_rectify_stats_get(sgmhip_engine* e, double* kernelMs, uint64_t* calls);
+
 int sgmhip_stats_reset(sgmhip_engine* e, int enable);
 int sgmhip_stats_get(sgmhip_engine* e, SGMHipStats* out);
 

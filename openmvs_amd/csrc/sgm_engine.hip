@@ -4,6 +4,7 @@
 #include "sgm_kernels_sub.hip"
 #include "sgm_post.hip"
 #include "sgm_tsgm.hip"
+#include "sgm_rectify.hip"
 #include "hip_buf.h"
 #include <math.h>
 #include <string.h>
@@ -28,6 +29,11 @@ struct sgmhip_engine : SGMProblemBufs {
 	bool uniform = false; int uniformMin = 0, uniformMax = 0; DevBuf<SGMUniform> d_uniform;   // every pixel has [uniformMin, uniformMax) and idx = pixel * nD (checked on the device at set_problem): the register-resident path kernel applies
 	int subGroups = 0;            // 0, or the lanes per sub-group (8, 16, 32): Match with the sub-group kernels of sgm_kernels_sub.hip (narrow, ragged ranges); see sgmhip_set_sub_group_kernels
 	struct Ev { hipEvent_t a, b; int kind; }; std::vector<Ev> events;
+	// the resident scene of the SGM path (sgmhip_scene_*): every image once, each with its own size (w = 0: never set), and the rectified pair of the last
+	// sgmhip_rectify_pair (rectW = 0: none) -- BGR, linear gray and validity mask of both sides, grown, never shrunk
+	struct SceneImage { DevBuf<unsigned char> bgr; int w = 0, h = 0; }; std::vector<SceneImage> scene;
+	DevBuf<unsigned char> d_rectBGR[2], d_rectMask[2]; DevBuf<float> d_rectGray[2], d_srgb; size_t capRect = 0; int rectW = 0, rectH = 0;
+	double rectMs = 0; uint64_t rectCalls = 0;     // HIP-event time of the rectification kernel since the last sgmhip_stats_reset
 };
 
 static void sgmFree(sgmhip_engine* e) {
@@ -39,7 +45,7 @@ static void evE(sgmhip_engine* e) { if (!e->statsOn) return; hipEventRecord(e->e
 static int sgmCollect(sgmhip_engine* e) {
 	if (e->events.empty()) return 0;
 	SGMCHK(e, hipStreamSynchronize(e->stream));
-	for (auto& ev : e->events) { float ms = 0; hipEventElapsedTime(&ms, ev.a, ev.b); (ev.kind == 0 ? e->stats.costMs : ev.kind == 1 ? e->stats.aggrMs : e->stats.wtaMs) += ms; hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
+	for (auto& ev : e->events) { float ms = 0; hipEventElapsedTime(&ms, ev.a, ev.b); (ev.kind == 0 ? e->stats.costMs : ev.kind == 1 ? e->stats.aggrMs : ev.kind == 2 ? e->stats.wtaMs : e->rectMs) += ms; if (ev.kind == 3) ++e->rectCalls; hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
 	e->events.clear();
 	return 0;
 }
@@ -79,6 +85,7 @@ void sgmhip_destroy(sgmhip_engine* e) {
 	hipSetDevice(e->device); hipStreamSynchronize(e->stream);
 	for (auto& ev : e->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
 	sgmFree(e); e->d_P2s.release(); e->d_uniform.release(); e->d_deltas.release();
+	e->scene.clear(); e->d_srgb.release(); for (int s = 0; s < 2; ++s) { e->d_rectBGR[s].release(); e->d_rectGray[s].release(); e->d_rectMask[s].release(); }
 	hipStreamDestroy(e->stream); delete e;
 }
 const char* sgmhip_last_error(sgmhip_engine* e) { return e ? e->err.c_str() : "null engine"; }
@@ -324,7 +331,7 @@ int sgmhip_set_sub_group_kernels(sgmhip_engine* e, int lanes) {
 	return 0;
 }
 int sgmhip_sync(sgmhip_engine* e) { if (!e) return SGMHIP_E_ARG; SGMCHK(e, hipSetDevice(e->device)); SGMCHK(e, hipStreamSynchronize(e->stream)); return 0; }
-int sgmhip_stats_reset(sgmhip_engine* e, int enable) { if (!e) return SGMHIP_E_ARG; hipSetDevice(e->device); sgmCollect(e); memset(&e->stats, 0, sizeof(e->stats)); e->statsOn = enable != 0; return 0; }
+int sgmhip_stats_reset(sgmhip_engine* e, int enable) { if (!e) return SGMHIP_E_ARG; hipSetDevice(e->device); sgmCollect(e); memset(&e->stats, 0, sizeof(e->stats)); e->rectMs = 0; e->rectCalls = 0; e->statsOn = enable != 0; return 0; }
 int sgmhip_stats_get(sgmhip_engine* e, SGMHipStats* out) { if (!e || !out) return SGMHIP_E_ARG; hipSetDevice(e->device); int rc = sgmCollect(e); if (rc) return rc; *out = e->stats; return 0; }
 
 // ---- tSGM steps around Match (SemiGlobalMatcher.cpp:1449-1811), see csrc/sgm_post.h ---------------------------------------------
@@ -596,29 +603,29 @@ int tsgmLevels(int w, int h, unsigned minResolution) {
 inline int cvRound(double v) { return (int)nearbyint(v); }      // cv::saturate_cast<int>(double): round half to even
 }
 
-int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* rightBGR, const float* leftGray, const float* rightGray,
-		const uint8_t* leftMask, const uint8_t* rightMask, int w, int h, unsigned minResolution, const int16_t* initLeftDisparity,
-		int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels) {
-	if (!e || !leftBGR || !rightBGR || !leftGray || !rightGray || !leftMask || !rightMask || !P2s || !disparity || !cost || w <= 0 || h <= 0 || nSpeckleSize < 0 ||
-	    subpixelMode < 0 || subpixelMode > SGMP_SUBPIXEL_LC_BLEND || subpixelSteps < 0 || subpixelSteps > 64) return SGMHIP_E_ARG;
+// the size rules of the loop: -> levels k (>= 1), or 0 with the engine's error text set
+static int tsgmCheckSize(sgmhip_engine* e, int w, int h, unsigned minResolution) {
 	const int k = tsgmLevels(w, h, minResolution);
-	if (k == 0) { e->err = "plain SGM (minResolution = 0) is not driven here: only tSGM"; return SGMHIP_E_ARG; }
-	if ((w % (1 << k)) || (h % (1 << k)) || (w >> k) <= 2 * SGM_HW + 2 || (h >> k) <= 2 * SGM_HW + 2) { e->err = "image size must be a multiple of 2^levels and its coarsest level larger than the window"; return SGMHIP_E_ARG; }
-	SGMCHK(e, hipSetDevice(e->device));
+	if (k == 0) { e->err = "plain SGM (minResolution = 0) is not driven here: only tSGM"; return 0; }
+	if ((w % (1 << k)) || (h % (1 << k)) || (w >> k) <= 2 * SGM_HW + 2 || (h >> k) <= 2 * SGM_HW + 2) { e->err = "image size must be a multiple of 2^levels and its coarsest level larger than the window"; return 0; }
+	return k;
+}
+
+// the loop on a rectified pair that is on the device already (full-resolution BGR, gray and masks of both sides): what sgmhip_tsgm_match runs after its uploads
+// and sgmhip_tsgm_match_rectified runs on the outputs of sgmhip_rectify_pair
+static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned char* fRB, const float* fLG, const float* fRG, const unsigned char* fLM, const unsigned char* fRM,
+		int w, int h, int k, const int16_t* initLeftDisparity, int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256],
+		int16_t* disparity, uint16_t* cost, int* numLevels) {
 	hipStream_t st = e->stream;
 	const size_t nFull = (size_t)w * h, nValid = (size_t)(w - 2 * SGM_HW) * (h - 2 * SGM_HW);
-	// full-resolution inputs and the per-level working set (sized for the finest level)
-	Scoped fLB, fRB, fLG, fRG, fLM, fRM, lB, rB, lG, rG, lM, rM, lM2, rM2, lD, rD, lDn, rDn, keys, ranges, tiles, scal, par, siz;
-	SGMCHK(e, fLB.alloc(nFull * 3)); SGMCHK(e, fRB.alloc(nFull * 3)); SGMCHK(e, fLG.alloc(nFull * 4)); SGMCHK(e, fRG.alloc(nFull * 4)); SGMCHK(e, fLM.alloc(nFull)); SGMCHK(e, fRM.alloc(nFull));
+	// the per-level working set (sized for the finest level)
+	Scoped lB, rB, lG, rG, lM, rM, lM2, rM2, lD, rD, lDn, rDn, keys, ranges, tiles, scal, par, siz;
 	SGMCHK(e, lB.alloc(nFull * 3)); SGMCHK(e, rB.alloc(nFull * 3)); SGMCHK(e, lG.alloc(nFull * 4)); SGMCHK(e, rG.alloc(nFull * 4));
 	SGMCHK(e, lM.alloc(nValid)); SGMCHK(e, rM.alloc(nValid)); SGMCHK(e, lM2.alloc(nValid)); SGMCHK(e, rM2.alloc(nValid));
 	SGMCHK(e, lD.alloc(nValid * 2)); SGMCHK(e, rD.alloc(nValid * 2)); SGMCHK(e, lDn.alloc(nValid * 2)); SGMCHK(e, rDn.alloc(nValid * 2));
 	SGMCHK(e, keys.alloc(nValid * 4)); SGMCHK(e, ranges.alloc(nValid * 4)); SGMCHK(e, par.alloc(nValid * 4)); SGMCHK(e, siz.alloc(nValid * 4));
 	const int maxTiles = (int)((nValid + SGMT_TILE - 1) / SGMT_TILE);
 	SGMCHK(e, tiles.alloc((size_t)maxTiles * 8)); SGMCHK(e, scal.alloc(16));
-	SGMCHK(e, hipMemcpyAsync(fLB.p, leftBGR, nFull * 3, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRB.p, rightBGR, nFull * 3, hipMemcpyHostToDevice, st));
-	SGMCHK(e, hipMemcpyAsync(fLG.p, leftGray, nFull * 4, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRG.p, rightGray, nFull * 4, hipMemcpyHostToDevice, st));
-	SGMCHK(e, hipMemcpyAsync(fLM.p, leftMask, nFull, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRM.p, rightMask, nFull, hipMemcpyHostToDevice, st));
 	SGMCHK(e, hipMemcpyAsync(e->d_P2s, P2s, 512, hipMemcpyHostToDevice, st));
 	e->maxP2 = 0; for (int i = 0; i < 256; ++i) e->maxP2 = std::max(e->maxP2, (int)P2s[i]);
 
@@ -667,12 +674,12 @@ int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* r
 		const int f = 1 << lvl, lw = w / f, lh = h / f, vw = lw - 2 * SGM_HW, vh = lh - 2 * SGM_HW;
 		const size_t nImg = (size_t)lw * lh, nV = (size_t)vw * vh;
 		const void *pLB, *pRB, *pLG, *pRG;
-		if (f == 1) { pLB = fLB.p; pRB = fRB.p; pLG = fLG.p; pRG = fRG.p; }
+		if (f == 1) { pLB = fLB; pRB = fRB; pLG = fLG; pRG = fRG; }
 		else {
-			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, (const unsigned char*)fLB.p, w, (unsigned char*)lB.p, lw, lh, f);
-			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, (const unsigned char*)fRB.p, w, (unsigned char*)rB.p, lw, lh, f);
-			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, (const float*)fLG.p, w, (float*)lG.p, lw, lh, f);
-			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, (const float*)fRG.p, w, (float*)rG.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, fLB, w, (unsigned char*)lB.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, fRB, w, (unsigned char*)rB.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, fLG, w, (float*)lG.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, fRG, w, (float*)rG.p, lw, lh, f);
 			pLB = lB.p; pRB = rB.p; pLG = lG.p; pRG = rG.p;
 		}
 		if (first) {
@@ -681,8 +688,8 @@ int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* r
 			if (dW <= 0 || dH <= 0) { e->err = "tsgm: coarsest level too small"; return SGMHIP_E_ARG; }
 			if (initLeftDisparity) SGMCHK(e, hipMemcpyAsync(leftDisp, initLeftDisparity, (size_t)dW * dH * 2, hipMemcpyHostToDevice, st));
 			else hipLaunchKernelGGL(sgmt_fill_i16_kernel, dim3(gridFor((size_t)dW * dH)), dim3(256), 0, st, leftDisp, (size_t)dW * dH, (short)SGMP_NO_DISP);
-			hipLaunchKernelGGL(sgmt_mask_first_kernel, dim3(gridFor(nV)), dim3(256), 0, st, (const unsigned char*)fLM.p, w, lm, vw, vh, f);   // :627-631
-			hipLaunchKernelGGL(sgmt_mask_first_kernel, dim3(gridFor(nV)), dim3(256), 0, st, (const unsigned char*)fRM.p, w, rm, vw, vh, f);
+			hipLaunchKernelGGL(sgmt_mask_first_kernel, dim3(gridFor(nV)), dim3(256), 0, st, fLM, w, lm, vw, vh, f);   // :627-631
+			hipLaunchKernelGGL(sgmt_mask_first_kernel, dim3(gridFor(nV)), dim3(256), 0, st, fRM, w, rm, vw, vh, f);
 		} else {
 			hipLaunchKernelGGL(sgmp_upscale_mask_kernel, dim3(gridFor(nV)), dim3(256), 0, st, (const uint8_t*)lm, mW, mH, lmNext, vw, vh);   // :634-635
 			hipLaunchKernelGGL(sgmp_upscale_mask_kernel, dim3(gridFor(nV)), dim3(256), 0, st, (const uint8_t*)rm, mW, mH, rmNext, vw, vh);
@@ -719,6 +726,128 @@ int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* r
 	SGMCHK(e, hipMemcpyAsync(cost, e->d_cost, nV * 2, hipMemcpyDeviceToHost, st));
 	SGMCHK(e, hipStreamSynchronize(st));
 	if (numLevels) *numLevels = levels;
+	return 0;
+}
+
+int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* rightBGR, const float* leftGray, const float* rightGray,
+		const uint8_t* leftMask, const uint8_t* rightMask, int w, int h, unsigned minResolution, const int16_t* initLeftDisparity,
+		int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels) {
+	if (!e || !leftBGR || !rightBGR || !leftGray || !rightGray || !leftMask || !rightMask || !P2s || !disparity || !cost || w <= 0 || h <= 0 || nSpeckleSize < 0 ||
+	    subpixelMode < 0 || subpixelMode > SGMP_SUBPIXEL_LC_BLEND || subpixelSteps < 0 || subpixelSteps > 64) return SGMHIP_E_ARG;
+	const int k = tsgmCheckSize(e, w, h, minResolution);
+	if (k == 0) return SGMHIP_E_ARG;
+	SGMCHK(e, hipSetDevice(e->device));
+	hipStream_t st = e->stream;
+	const size_t nFull = (size_t)w * h;
+	DevBuf<unsigned char> fLB, fRB, fLM, fRM; DevBuf<float> fLG, fRG;          // the full-resolution inputs
+	SGMCHK(e, fLB.alloc(nFull * 3)); SGMCHK(e, fRB.alloc(nFull * 3)); SGMCHK(e, fLG.alloc(nFull)); SGMCHK(e, fRG.alloc(nFull)); SGMCHK(e, fLM.alloc(nFull)); SGMCHK(e, fRM.alloc(nFull));
+	SGMCHK(e, hipMemcpyAsync(fLB, leftBGR, nFull * 3, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRB, rightBGR, nFull * 3, hipMemcpyHostToDevice, st));
+	SGMCHK(e, hipMemcpyAsync(fLG, leftGray, nFull * 4, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRG, rightGray, nFull * 4, hipMemcpyHostToDevice, st));
+	SGMCHK(e, hipMemcpyAsync(fLM, leftMask, nFull, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRM, rightMask, nFull, hipMemcpyHostToDevice, st));
+	return tsgmRun(e, fLB, fRB, fLG, fRG, fLM, fRM, w, h, k, initLeftDisparity, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
+}
+
+// ---- the resident SGM scene: every image uploaded once, pairs rectified on the device (kernel in sgm_rectify.hip) ---------------------------------------------
+int sgmhip_scene_create(sgmhip_engine* e, int nImages) {
+	if (!e) return SGMHIP_E_ARG;
+	if (nImages <= 0) { e->err = "scene_create: the number of images must be positive"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	e->scene.clear(); e->scene.resize((size_t)nImages);
+	return 0;
+}
+
+int sgmhip_scene_set_image(sgmhip_engine* e, int idx, const uint8_t* bgr, int w, int h) {
+	if (!e) return SGMHIP_E_ARG;
+	if (idx < 0 || (size_t)idx >= e->scene.size()) { e->err = "scene_set_image: image index " + std::to_string(idx) + " is outside the scene table of " + std::to_string(e->scene.size()); return SGMHIP_E_ARG; }
+	if (!bgr || w <= 0 || h <= 0) { e->err = "scene_set_image: no pixels, or a width or height <= 0"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	sgmhip_engine::SceneImage& im = e->scene[(size_t)idx];
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	im.w = im.h = 0;
+	SGMCHK(e, im.bgr.alloc((size_t)w * h * 3));
+	SGMCHK(e, hipMemcpyAsync(im.bgr, bgr, (size_t)w * h * 3, hipMemcpyHostToDevice, e->stream));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	im.w = w; im.h = h;
+	return 0;
+}
+
+int sgmhip_scene_clear(sgmhip_engine* e) {
+	if (!e) return SGMHIP_E_ARG;
+	SGMCHK(e, hipSetDevice(e->device));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	e->scene.clear();
+	return 0;
+}
+
+int sgmhip_rectify_pair(sgmhip_engine* e, int idxLeft, int idxRight, const double invH1[9], const double invH2[9], int w, int h, const float srgb2lin[256]) {
+	if (!e) return SGMHIP_E_ARG;
+	if (!invH1 || !invH2 || !srgb2lin) { e->err = "rectify_pair: null homography or table"; return SGMHIP_E_ARG; }
+	const int idx[2] = {idxLeft, idxRight};
+	for (int s = 0; s < 2; ++s) {
+		if (idx[s] < 0 || (size_t)idx[s] >= e->scene.size()) { e->err = "rectify_pair: image index " + std::to_string(idx[s]) + " is outside the scene table of " + std::to_string(e->scene.size()); return SGMHIP_E_ARG; }
+		if (!e->scene[(size_t)idx[s]].w) { e->err = "rectify_pair: image " + std::to_string(idx[s]) + " was never set"; return SGMHIP_E_ARG; }
+	}
+	if (w <= 0 || h <= 0) { e->err = "rectify_pair: the rectified width and height must be positive"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	hipStream_t st = e->stream;
+	const size_t n = (size_t)w * h;
+	e->rectW = e->rectH = 0;
+	if (n > e->capRect) {
+		SGMCHK(e, hipStreamSynchronize(st));
+		for (int s = 0; s < 2; ++s) { SGMCHK(e, e->d_rectBGR[s].alloc(n * 3)); SGMCHK(e, e->d_rectGray[s].alloc(n)); SGMCHK(e, e->d_rectMask[s].alloc(n)); }
+		e->capRect = n;
+	}
+	if (!e->d_srgb) SGMCHK(e, e->d_srgb.alloc(256));
+	SGMCHK(e, hipMemcpyAsync(e->d_srgb, srgb2lin, 256 * sizeof(float), hipMemcpyHostToDevice, st));
+	SGMRectPair pair;
+	for (int s = 0; s < 2; ++s) {
+		const sgmhip_engine::SceneImage& im = e->scene[(size_t)idx[s]];
+		SGMRectSide& o = pair.s[s];
+		o.src = im.bgr; o.W0 = im.w; o.H0 = im.h;
+		memcpy(o.Hi, s ? invH2 : invH1, sizeof(o.Hi));
+		o.bgr = e->d_rectBGR[s]; o.gray = e->d_rectGray[s]; o.mask = e->d_rectMask[s];
+	}
+	evB(e, 3);
+	hipLaunchKernelGGL(sgm_rectify_pair_kernel, dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4), 2), dim3(64, 4), 0, st, pair, w, h, (const float*)e->d_srgb);
+	evE(e);
+	SGMCHK(e, hipGetLastError());
+	SGMCHK(e, hipStreamSynchronize(st));          // srgb2lin is the caller's memory
+	e->rectW = w; e->rectH = h;
+	return 0;
+}
+
+int sgmhip_rectified_get(sgmhip_engine* e, int side, uint8_t* bgr, float* gray, uint8_t* mask) {
+	if (!e) return SGMHIP_E_ARG;
+	if (side < 0 || side > 1) { e->err = "rectified_get: side must be 0 (left) or 1 (right)"; return SGMHIP_E_ARG; }
+	if (!e->rectW) { e->err = "no rectified pair is resident: call sgmhip_rectify_pair first"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	const size_t n = (size_t)e->rectW * e->rectH;
+	if (bgr) SGMCHK(e, hipMemcpyAsync(bgr, e->d_rectBGR[side], n * 3, hipMemcpyDeviceToHost, e->stream));
+	if (gray) SGMCHK(e, hipMemcpyAsync(gray, e->d_rectGray[side], n * 4, hipMemcpyDeviceToHost, e->stream));
+	if (mask) SGMCHK(e, hipMemcpyAsync(mask, e->d_rectMask[side], n, hipMemcpyDeviceToHost, e->stream));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	return 0;
+}
+
+int sgmhip_tsgm_match_rectified(sgmhip_engine* e, unsigned minResolution, const int16_t* initLeftDisparity, int nSpeckleSize, int subpixelMode, int subpixelSteps,
+		uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels) {
+	if (!e) return SGMHIP_E_ARG;
+	if (!P2s || !disparity || !cost || nSpeckleSize < 0 || subpixelMode < 0 || subpixelMode > SGMP_SUBPIXEL_LC_BLEND || subpixelSteps < 0 || subpixelSteps > 64) { e->err = "tsgm_match_rectified: null pointer or option out of range"; return SGMHIP_E_ARG; }
+	if (!e->rectW) { e->err = "no rectified pair is resident: call sgmhip_rectify_pair first"; return SGMHIP_E_ARG; }
+	const int k = tsgmCheckSize(e, e->rectW, e->rectH, minResolution);
+	if (k == 0) return SGMHIP_E_ARG;
+	SGMCHK(e, hipSetDevice(e->device));
+	return tsgmRun(e, e->d_rectBGR[0], e->d_rectBGR[1], e->d_rectGray[0], e->d_rectGray[1], e->d_rectMask[0], e->d_rectMask[1], e->rectW, e->rectH, k,
+	               initLeftDisparity, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
+}
+
+int sgmhip_rectify_stats_get(sgmhip_engine* e, double* kernelMs, uint64_t* calls) {
+	if (!e) return SGMHIP_E_ARG;
+	hipSetDevice(e->device);
+	const int rc = sgmCollect(e); if (rc) return rc;
+	if (kernelMs) *kernelMs = e->rectMs;
+	if (calls) *calls = e->rectCalls;
 	return 0;
 }
 

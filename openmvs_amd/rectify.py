@@ -83,23 +83,33 @@ def warp_perspective_u8(img, H, size):
     return out.reshape((h, w) + img.shape[2:]), np.where(inside, 255, 0).astype(np.uint8)
 
 
-def stereo_rectify_images(img1, K1, R1w, C1, img2, K2, R2w, C2, points1, points2):
-    """Image::StereoRectifyImages.  img*: (h, w, 3) uint8 BGR; points*: (n,3) projections (x, y, depth) of the sparse points both images see.
-    -> dict(rect1, rect2, mask1, mask2, H (3x3, original -> rectified left), Q (4x4), size) or None if the baseline vanishes."""
+def stereo_rectify_geometry(size1, K1, R1w, C1, size2, K2, R2w, C2, points1, points2):
+    """The geometry of Image::StereoRectifyImages without touching a pixel.  size*: (w, h) of the two images; points*: (n,3) projections
+    (x, y, depth) of the sparse points both images see.
+    -> dict(H1, H2 (3x3, original -> rectified), Q (4x4), size (w, h of both rectified images), t, K1r, K2r, R1, R2) or None if the baseline vanishes."""
     R1, R2, K1r, K2r, t = stereo_rectify_fusiello(K1, R1w, C1, K2, R2w, C2)
     if abs(t) < 1e-7:
         return None
-    size1 = (img1.shape[1], img1.shape[0]); size2 = (img2.shape[1], img2.shape[0])
+    size1 = (int(size1[0]), int(size1[1])); size2 = (int(size2[0]), int(size2[1]))
     size = size1
     if len(points1):
         K1r, K2r, size = set_rectification_roi(np.asarray(points1, np.float32), np.asarray(points2, np.float32), size1, size2,
                                                np.asarray(K1, np.float64), np.asarray(K2, np.float64), R1, R2, K1r, K2r)
     H1 = K1r @ R1 @ _inv_k(np.asarray(K1, np.float64)); H2 = K2r @ R2 @ _inv_k(np.asarray(K2, np.float64))
-    rect1, mask1 = warp_perspective_u8(img1, H1, size); rect2, mask2 = warp_perspective_u8(img2, H2, size)
     Q = np.zeros((4, 4))                                               # Q * [x, y, disparity, 1] = [X, Y, Z, 1] * w in camera-1 coordinates (:326-337)
     Q[0, 0] = Q[1, 1] = 1; Q[0, 3] = -K1r[0, 2]; Q[1, 3] = -K1r[1, 2]; Q[2, 3] = K1r[0, 0]; Q[3, 2] = -1.0 / t; Q[3, 3] = (K1r[0, 2] - K2r[0, 2]) / t
     P = np.eye(4); P[:3, :3] = np.asarray(K1, np.float64) @ R1.T       # ... then into the original image 1 (:339-342)
-    return dict(rect1=rect1, rect2=rect2, mask1=mask1, mask2=mask2, H=H1, Q=P @ Q, size=size, t=t, K1=K1r, K2=K2r, R1=R1, R2=R2)
+    return dict(H1=H1, H2=H2, Q=P @ Q, size=size, t=t, K1r=K1r, K2r=K2r, R1=R1, R2=R2)
+
+
+def stereo_rectify_images(img1, K1, R1w, C1, img2, K2, R2w, C2, points1, points2):
+    """Image::StereoRectifyImages.  img*: (h, w, 3) uint8 BGR; points*: (n,3) projections (x, y, depth) of the sparse points both images see.
+    -> dict(rect1, rect2, mask1, mask2, H (3x3, original -> rectified left), Q (4x4), size) or None if the baseline vanishes."""
+    g = stereo_rectify_geometry((img1.shape[1], img1.shape[0]), K1, R1w, C1, (img2.shape[1], img2.shape[0]), K2, R2w, C2, points1, points2)
+    if g is None:
+        return None
+    rect1, mask1 = warp_perspective_u8(img1, g["H1"], g["size"]); rect2, mask2 = warp_perspective_u8(img2, g["H2"], g["size"])
+    return dict(rect1=rect1, rect2=rect2, mask1=mask1, mask2=mask2, H=g["H1"], Q=g["Q"], size=g["size"], t=g["t"], K1=g["K1r"], K2=g["K2r"], R1=g["R1"], R2=g["R2"])
 
 
 def scale_stereo_rectification(H, Q, scale):

@@ -14,7 +14,9 @@ EXPORTS = ["sgmhip_create", "sgmhip_destroy", "sgmhip_last_error", "sgmhip_gener
            "sgmhip_match", "sgmhip_get_results", "sgmhip_sync", "sgmhip_stats_reset", "sgmhip_stats_get",
            "sgmhip_consistency_cross_check", "sgmhip_filter_by_cost", "sgmhip_extract_mask", "sgmhip_upscale_mask", "sgmhip_flip_direction",
            "sgmhip_refine_disparity", "sgmhip_disparity2range_map", "sgmhip_depth2disparity_map", "sgmhip_disparity2depth_map",
-           "sgmhip_project_disparity2depth_map", "sgmhip_fuse_pairs", "sgmhip_filter_speckles", "sgmhip_set_disparity", "sgmhip_tsgm_match", "sgmhip_fuse_disparities", "sgmhip_set_sub_group_kernels"]
+           "sgmhip_project_disparity2depth_map", "sgmhip_fuse_pairs", "sgmhip_filter_speckles", "sgmhip_set_disparity", "sgmhip_tsgm_match", "sgmhip_fuse_disparities", "sgmhip_set_sub_group_kernels",
+           "sgmhip_scene_create", "sgmhip_scene_set_image", "sgmhip_scene_clear", "sgmhip_rectify_pair", "sgmhip_rectified_get", "sgmhip_tsgm_match_rectified",
+           "sgmhip_rectify_stats_get"]
 NO_DISP = 32767          # SemiGlobalMatcher::NO_DISP
 INVALID, VALID = 0, 255  # MaskMap values
 SUBPIXEL_NA, SUBPIXEL_LINEAR, SUBPIXEL_POLY4, SUBPIXEL_PARABOLA, SUBPIXEL_SINE, SUBPIXEL_COSINE, SUBPIXEL_LC_BLEND = range(7)
@@ -75,6 +77,8 @@ class SemiGlobalMatcherHIP:
             raise SGMError(f"sgmhip_create failed ({rc}): no usable HIP device")
         self.P1 = P1
         self.P2s = generate_p2s(P2, P2alpha, P2beta)
+        self.image_uploads = 0        # images sent to the device by scene_set_images since the engine was created
+        self._rect_shape = None
 
     def _chk(self, rc):
         if rc != 0:
@@ -206,6 +210,62 @@ class SemiGlobalMatcherHIP:
                                               c.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(lv)))
         self._shape = d.shape
         return d, c, int(lv.value)
+
+    # ---- the resident scene: images uploaded once, pairs rectified on the device ------------------------------------------------------------
+    def scene_set_images(self, images):
+        """Replace the resident scene by `images` ((h, w, 3) uint8 BGR, each with its own size; None leaves a slot unset): one upload per image."""
+        images = list(images)
+        self._rect_shape = None
+        self._chk(self._lib.sgmhip_scene_create(self._h, len(images)))
+        for i, im in enumerate(images):
+            if im is None:
+                continue
+            a = np.ascontiguousarray(im, np.uint8)
+            assert a.ndim == 3 and a.shape[2] == 3
+            self._chk(self._lib.sgmhip_scene_set_image(self._h, i, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]))
+            self.image_uploads += 1
+
+    def scene_clear(self):
+        self._rect_shape = None
+        self._chk(self._lib.sgmhip_scene_clear(self._h))
+
+    def rectify_pair(self, idx_left, idx_right, inv_h1, inv_h2, size, srgb2lin):
+        """Warp images idx_left / idx_right of the resident scene by the inverse homographies inv_h1 / inv_h2 into size = (w, h), with their linear gray
+        images and validity masks (sgmhip_rectify_pair: rectify.warp_perspective_u8 + sgm_pipeline.to_gray_linear, bit for bit).  The results stay on
+        the device for `tsgm_match_rectified` / `rectified`."""
+        a = np.ascontiguousarray(inv_h1, np.float64); b = np.ascontiguousarray(inv_h2, np.float64); t = np.ascontiguousarray(srgb2lin, np.float32)
+        assert a.shape == (3, 3) and b.shape == (3, 3) and t.shape == (256,)
+        w, h = int(size[0]), int(size[1])
+        self._chk(self._lib.sgmhip_rectify_pair(self._h, int(idx_left), int(idx_right), a.ctypes.data_as(C.POINTER(C.c_double)), b.ctypes.data_as(C.POINTER(C.c_double)),
+                                                w, h, t.ctypes.data_as(C.POINTER(C.c_float))))
+        self._rect_shape = (h, w)
+
+    def rectified(self, side, bgr=True, gray=True, mask=True):
+        """-> (bgr, gray, mask) of the resident rectified image of `side` (0 left, 1 right); None for what was not asked."""
+        if self._rect_shape is None:
+            self._chk(self._lib.sgmhip_rectified_get(self._h, int(side), None, None, None))      # the library's own error
+        h, w = self._rect_shape or (0, 0)
+        b = np.zeros((h, w, 3), np.uint8) if bgr else None; g = np.zeros((h, w), np.float32) if gray else None; m = np.zeros((h, w), np.uint8) if mask else None
+        self._chk(self._lib.sgmhip_rectified_get(self._h, int(side), None if b is None else b.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 None if g is None else g.ctypes.data_as(C.POINTER(C.c_float)), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return b, g, m
+
+    def tsgm_match_rectified(self, min_resolution=320, init_left_disparity=None, n_speckle_size=100, subpixel_mode=SUBPIXEL_LC_BLEND, subpixel_steps=4):
+        """`tsgm_match` on the resident rectified pair of the last `rectify_pair`.  -> (disparity, cost, levels) on the valid grid."""
+        h, w = self._rect_shape or (6, 6)              # (without a pair the library refuses the call)
+        init = None if init_left_disparity is None else np.ascontiguousarray(init_left_disparity, np.int16)
+        d = np.zeros((h - 6, w - 6), np.int16); c = np.zeros((h - 6, w - 6), np.uint16); lv = C.c_int(0)
+        self._chk(self._lib.sgmhip_tsgm_match_rectified(self._h, C.c_uint(min_resolution), None if init is None else init.ctypes.data_as(C.POINTER(C.c_int16)), n_speckle_size,
+                                                        subpixel_mode, subpixel_steps, C.c_uint16(self.P1), self.P2s.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                        d.ctypes.data_as(C.POINTER(C.c_int16)), c.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(lv)))
+        self._shape = d.shape
+        return d, c, int(lv.value)
+
+    def rectify_stats(self):
+        """-> (HIP-event milliseconds of the rectification kernel, its launches) since the last stats_reset(True)."""
+        ms = C.c_double(0); n = C.c_uint64(0)
+        self._chk(self._lib.sgmhip_rectify_stats_get(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def fuse_disparities(self, pairs, size, minViews=2):
         """SemiGlobalMatcher::Fuse in one resident call.  pairs: dicts with disparity, cost, Q, subpixel_steps (the .dimap content); size = (w, h) of

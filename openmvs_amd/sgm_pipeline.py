@@ -48,36 +48,55 @@ def compute_resize(size, scale):
     return int(np.rint(size[0] * scale)), int(np.rint(size[1] * scale))
 
 
-def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, subpixel_steps=4, seed_depth=None):
+def rectifies_on_device(be):
+    """The backend keeps the scene's images resident and rectifies pairs itself (`SemiGlobalMatcherHIP.scene_set_images` / `rectify_pair` /
+    `tsgm_match_rectified`), and was not told to leave that to the host (`DeviceBackend(..., rectify_on_device=False)`)."""
+    return all(hasattr(be, n) for n in ("scene_set_images", "rectify_pair", "tsgm_match_rectified")) and bool(getattr(be, "rectify_on_device", True))
+
+
+def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, subpixel_steps=4, seed_depth=None, image_ids=None):
     """One pair of `Match(scene, ...)`: cam = (K, R, C).  Returns the `.dimap` content: dict(disparity, cost, H, Q, image_size, subpixel_steps)
     or None if the pair cannot be rectified.
 
     seed_depth: callable (w, h) -> depth map of image A at that size, the rough estimate from the sparse points that the reference makes with
     `TriangulatePoints2DepthMap(..., bAddCorners = true)` (SemiGlobalMatcher.cpp:608-618; `views.triangulate_points_depth_map` or
     `mvsf_triangulate_depth_map`); it becomes the first level's initial disparities through Depth2DisparityMap (`:619-625`).  Without it the
-    first level searches the default range around zero."""
+    first level searches the default range around zero.
+
+    image_ids: (a, b), the slots of the two images in the backend's resident scene (`be.scene_set_images`).  With them and a backend that
+    rectifies (`rectifies_on_device`) the pair is warped, converted to gray and matched on the device and no image travels; otherwise the host
+    warps (`rectify.stereo_rectify_images`) and the six images are uploaded for the loop.  Both routes give the same result."""
     p1 = world_to_image3(*camA, shared_points); p2 = world_to_image3(*camB, shared_points)
-    r = rectify.stereo_rectify_images(bgrA, *camA, bgrB, *camB, p1, p2)
+    on_device = image_ids is not None and rectifies_on_device(be)
+    if on_device:
+        r = rectify.stereo_rectify_geometry((bgrA.shape[1], bgrA.shape[0]), *camA, (bgrB.shape[1], bgrB.shape[0]), *camB, p1, p2)
+    else:
+        r = rectify.stereo_rectify_images(bgrA, *camA, bgrB, *camB, p1, p2)
     if r is None:
         return None
+    H = r["H1"] if on_device else r["H"]
     k = tsgm.compute_scale(r["size"][0], r["size"][1], min_resolution)
     f = 1 << k
     w, h = r["size"][0] // f * f, r["size"][1] // f * f           # the loop's 8-bit resampler wants multiples of 2^levels: crop right / bottom
-    lb, rb = r["rect1"][:h, :w].copy(), r["rect2"][:h, :w].copy()
     init = None
     if seed_depth is not None:
         s = 0.5 / f                                               # scale * 0.5
         depth = seed_depth(*compute_resize((bgrA.shape[1], bgrA.shape[0]), s))
-        H2, Q2 = rectify.scale_stereo_rectification(r["H"], r["Q"], s)
+        H2, Q2 = rectify.scale_stereo_rectification(H, r["Q"], s)
         hw, hh = compute_resize((w // f, h // f), 0.5)
         init = be.Depth2DisparityMap(depth, np.linalg.inv(H2), np.linalg.inv(Q2), 1, (hw - 2 * tsgm.HW, hh - 2 * tsgm.HW))
+    if on_device:                                                 # sgmhip_rectify_pair + sgmhip_tsgm_match_rectified: the crop leaves the pixel coordinates as they are
+        be.rectify_pair(image_ids[0], image_ids[1], np.linalg.inv(r["H1"]), np.linalg.inv(r["H2"]), (w, h), _srgb_table())
+        disp, cost, _ = be.tsgm_match_rectified(min_resolution=min_resolution, init_left_disparity=init, subpixel_steps=subpixel_steps)
+        return dict(disparity=disp, cost=cost, H=H, Q=r["Q"], image_size=(bgrA.shape[1], bgrA.shape[0]), subpixel_steps=subpixel_steps, seeded=init is not None)
+    lb, rb = r["rect1"][:h, :w].copy(), r["rect2"][:h, :w].copy()
     args = (lb, to_gray_linear(lb), rb, to_gray_linear(rb), r["mask1"][:h, :w].copy(), r["mask2"][:h, :w].copy())
     if hasattr(be, "tsgm_match"):                                 # the device runs the whole loop in one resident call (sgmhip_tsgm_match)
         disp, cost, _ = be.tsgm_match(args[0], args[2], args[1], args[3], args[4], args[5], min_resolution=min_resolution, init_left_disparity=init,
                                       subpixel_steps=subpixel_steps)
     else:
         disp, cost, _ = tsgm.tsgm_match(be, *args, min_resolution=min_resolution, init_left_disparity=init, subpixel_steps=subpixel_steps)
-    return dict(disparity=disp, cost=cost, H=r["H"], Q=r["Q"], image_size=(bgrA.shape[1], bgrA.shape[0]), subpixel_steps=subpixel_steps, seeded=init is not None)
+    return dict(disparity=disp, cost=cost, H=H, Q=r["Q"], image_size=(bgrA.shape[1], bgrA.shape[0]), subpixel_steps=subpixel_steps, seeded=init is not None)
 
 
 def fuse_pairs(be, pairs, min_views=2):
@@ -161,11 +180,17 @@ def match_scene(be, sc, cams, bgr, neighbors, out_dir, n_views=0, f_min_score_ra
         return seen[i]
 
     cam = lambda i: (cams.K[i], cams.R[i], cams.C[i])
+    listed = {i: _listed(neighbors[i], n_views, f_min_score_ratio, f_min_score) for i in sorted(neighbors)}
+    resident = False                                             # the images this run touches are in the backend's scene (uploaded before the first pair, once)
     done = []
     for i in sorted(neighbors):
-        for j in _listed(neighbors[i], n_views, f_min_score_ratio, f_min_score):
+        for j in listed[i]:
             if os.path.exists(os.path.join(out_dir, pair_file_name(i, j))) or os.path.exists(os.path.join(out_dir, pair_file_name(j, i))):
                 continue
+            if not resident and rectifies_on_device(be):
+                used = set(listed) | {j_ for js in listed.values() for j_ in js}
+                be.scene_set_images([bgr[v] if v in used else None for v in range(max(used) + 1)])
+                resident = True
             pts = np.nonzero(sees(i))[0]
 
             def seed(w, h, i=i, pts=pts):
@@ -174,11 +199,13 @@ def match_scene(be, sc, cams, bgr, neighbors, out_dir, n_views=0, f_min_score_ra
                 return views.triangulate_points_depth_map(K, P, sc.vertices[pts], w, h, avg_depth=None if avg_depth is None else avg_depth[i])[0]
 
             p = match_pair(be, bgr[i], cam(i), bgr[j], cam(j), sc.vertices[sees(i) & sees(j)], min_resolution=min_resolution, subpixel_steps=subpixel_steps,
-                           seed_depth=seed if (avg_depth is not None and len(pts) >= 3) else None)
+                           seed_depth=seed if (avg_depth is not None and len(pts) >= 3) else None, image_ids=(i, j) if resident else None)
             if p is None:
                 continue                                         # the pair cannot be rectified (:566-567)
             dmap.save_dimap(os.path.join(out_dir, pair_file_name(i, j)), p["image_size"], p["H"], p["Q"], p["subpixel_steps"], p["disparity"], p["cost"])
             done.append((i, j))
+    if resident:
+        be.scene_clear()
     return done
 
 
@@ -214,10 +241,12 @@ def fuse_scene(be, cams, sizes, neighbors, pair_dir, n_views=0, f_min_score_rati
 
 class DeviceBackend:
     """The device behind `match_pair` / `fuse_pairs`: `sgm.SemiGlobalMatcherHIP` has every step of the interface (and the resident loop and fusion, `tsgm_match`,
-    `fuse_disparities`) except the float area resampler of the image pyramid, which the PatchMatch library provides (`PatchMatchHIP.resize`)."""
+    `fuse_disparities`) except the float area resampler of the image pyramid, which the PatchMatch library provides (`PatchMatchHIP.resize`).
+    rectify_on_device: keep the scene's images resident and rectify every pair on the device (`match_scene`, `match_pair`); False leaves the warps and the gray
+    conversion to the host and uploads each pair's images for the loop -- the same results, for A/B runs and tests."""
 
-    def __init__(self, matcher, engine):
-        self.m, self.e = matcher, engine
+    def __init__(self, matcher, engine, rectify_on_device=True):
+        self.m, self.e, self.rectify_on_device = matcher, engine, bool(rectify_on_device)
 
     def resize_area_f32(self, img, f):
         return self.e.resize(0, img, f)
@@ -238,10 +267,8 @@ def dense_reconstruction(be, mvs_in, out_dir, fusion_mode, opt=None, image_loade
         raise ValueError("the SGM path is fusion modes -1 and -2")
     opt = opt or optdense.defaults()
     sv = densify.load_scene(mvs_in, opt=opt, image_loader=image_loader)
-    if sv.alias_of or len(set(map(tuple, sv.sizes))) > 1:
-        raise NotImplementedError("the SGM driver takes scenes whose images share one size")
     sc = mvsi.load(mvs_in)
-    cams = views.Cameras(sc, sv.sizes)
+    cams = views.Cameras(sc, sv.sizes[:len(sc.images)])          # every image at its own size; the slots behind them are PatchMatch's resampled neighbour copies
     nbs = {i: sv.all_view_scores[i] for i in sv.ids if len(sv.all_view_scores.get(i, ()))}
     args = dict(n_views=int(opt.nNumViews), f_min_score_ratio=float(opt.fViewMinScoreRatio), f_min_score=float(opt.fViewMinScore))
     if fusion_mode == -1:

@@ -1,5 +1,5 @@
-"""Register / LDS / scratch / occupancy of every kernel of libpmhip.so as the compiler reports them (no GPU needed):
-    python tools/kernel_resources.py [-DPM_TCX=10 ...]
+"""Register / LDS / scratch / occupancy of every kernel of libpmhip.so (or `--lib=libsgmhip.so`) as the compiler reports them (no GPU needed):
+    python tools/kernel_resources.py [--lib=libsgmhip.so] [-DPM_TCX=10 ...]
 Used by tests/test_kernel_resources.py to pin the figures DESIGN.md quotes for the sweep kernel."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +26,8 @@ def resources(extra_flags=(), lib="libpmhip.so"):
 
 
 if __name__ == "__main__":
-    r = resources(sys.argv[1:])
+    lib = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--lib=")] or ["libpmhip.so"])[-1]
+    r = resources([a for a in sys.argv[1:] if not a.startswith("--lib=")], lib=lib)
     for k in sorted(r):
         v = r[k]
         print("%-70s VGPR %3d SGPR %3d scratch %3d B  occupancy %d  LDS %5d B" % (k[:70], v["vgpr"], v["sgpr"], v["scratch"], v["occupancy"], v["lds"]))
