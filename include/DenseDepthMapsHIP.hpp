@@ -51,6 +51,10 @@ public:
 		const float* gray = nullptr;            // w*h, gray in [0,1] (Image::toGray), row-major
 		const unsigned char* bgr = nullptr;     // w*h*3 or null (needed for FuseDepthMaps with bEstimateColor)
 		const unsigned char* mask = nullptr;    // w*h or null: 0 = ignored pixel (--ignore-mask-label, DepthMap.cpp:296-323)
+		// Instead of `gray` and `bgr`: the decoded 8-bit image at its stored size, W0*H0*3 bytes, channelOrder 0 = B,G,R / 1 = R,G,B.  The device brings it to this view's
+		// working size (Image::ResizeImage; see WorkingSize) and converts it (TImage::toGray) through the engine's image store: a host without OpenMVS needs neither
+		// (pmhip_image_prepare, pmhip_scene_set_view_stored).  The image is read during LoadScene only.
+		const unsigned char* image8 = nullptr; int W0 = 0, H0 = 0, channelOrder = 0;
 		double K[9], R[9], C[3];                // pixel camera of this image: x = K R (X - C)
 		float dMin = 0, dMax = 0;               // depth range of the sparse points seen by the view (DepthData::dMin/dMax)
 		std::vector<int32_t> neighbors;         // indices into the view array, best first (DepthData::neighbors after SelectViews)
@@ -86,6 +90,13 @@ public:
 		bool anyMask = false;
 		for (int i = 0; i < n; ++i) {
 			const View& v = views[i];
+			if (v.image8) {                                                     // decoded image -> store entry i -> the view's own copies; the entry goes at once
+				check(pmhip_image_prepare(e_, i, v.image8, v.W0, v.H0, v.channelOrder, v.w > 0 ? v.w : w, v.h > 0 ? v.h : h));
+				check(pmhip_scene_set_view_stored(e_, i, i, v.K, v.R, v.C, v.dMin, v.dMax, v.neighbors.data(), (int)v.neighbors.size()));
+				check(pmhip_image_drop(e_, i));
+				if (v.mask) { check(pmhip_scene_set_mask(e_, i, v.mask)); anyMask = true; }
+				continue;
+			}
 			if (!v.gray) throw std::runtime_error("DenseDepthMapsHIP: view without an image");
 			if (v.w > 0 && v.h > 0 && (v.w != w || v.h != h))
 				check(pmhip_scene_set_view_sized(e_, i, v.gray, v.w, v.h, 0, v.K, v.R, v.C, v.dMin, v.dMax, v.neighbors.data(), (int)v.neighbors.size()));
@@ -97,6 +108,12 @@ public:
 		(void)anyMask;
 		ids_.resize((size_t)n);
 		for (int i = 0; i < n; ++i) ids_[(size_t)i] = i;
+	}
+
+	// The size Image::ResizeImage brings a W0 x H0 image to under OPTDENSE::nResolutionLevel / nMinResolution / nMaxResolution (pmhip_working_size): View::w, View::h of
+	// a view given as image8, and the size its camera is scaled to (Image::UpdateCamera; mvsf_camera of include/mvsfront.h)
+	static void WorkingSize(int W0, int H0, unsigned nResolutionLevel, unsigned nMinResolution, unsigned nMaxResolution, int& w, int& h) {
+		if (pmhip_working_size(W0, H0, nResolutionLevel, nMinResolution, nMaxResolution, &w, &h) != PMHIP_OK) throw std::runtime_error("DenseDepthMapsHIP: bad image size");
 	}
 
 	// Scene::ComputeDepthMaps: all rounds for all views, then the post-filters the option bits ask for.  Returns the number of depth maps.
@@ -147,7 +164,7 @@ public:
 		PMHipFuseParams fp;
 		fp.nMinViewsFuse = opt.nMinViewsFuse; fp.fDepthDiffThreshold = opt.fDepthDiffThreshold; fp.fNormalDiffThreshold = opt.fNormalDiffThreshold;
 		bool haveColor = opt.bEstimateColor;
-		for (const View& v : views) haveColor = haveColor && v.bgr != nullptr;
+		for (const View& v : views) haveColor = haveColor && (v.bgr != nullptr || v.image8 != nullptr);   // (an image8 view got its colour image from the store)
 		fp.bEstimateColor = haveColor ? 1 : 0; fp.bEstimateNormal = opt.bEstimateNormal ? 1 : 0;
 		uint64_t nP = 0, nV = 0, nD = 0;
 		chk(pmhip_scene_fuse(e, order.data(), (int)order.size(), &fp, &nP, &nV, &nD));

@@ -267,6 +267,41 @@ int pmhip_scene_images_updated(pmhip_engine* e);
  * (DepthData::IsValid(), SceneDensify.cpp:2150-2163).  pmhip_scene_estimate, _set_maps and _copy(what == 1, toEngine) do this themselves; a raw
  * pointer write cannot, and such neighbours would be skipped without this call. */
 int pmhip_scene_maps_updated(pmhip_engine* e, int firstIdx, int count);
+/* ---- 2b. the image store: working-resolution images made on the device from decoded 8-bit images -------------------------------------
+ * The caller hands a decoded image at its stored size over once; the device produces what Image::ResizeImage (libs/MVS/Image.cpp:139-155: cv::resize INTER_AREA,
+ * shrinking only) and TImage::toGray (libs/Common/Types.inl:2377-2425) produce -- the 8-bit BGR image and the gray float image at the working size -- and the
+ * resampled neighbour copies of DepthData::ViewData::ScaleImage (libs/MVS/DepthMap.h:193-204: INTER_AREA below 1, INTER_CUBIC above).  A scene view adopts an
+ * entry by a device-to-device copy.  The store is independent of the scene: pmhip_scene_create leaves it alone (images are prepared before the scene's slot count
+ * is known) and pmhip_scene_bytes does not count it; pmhip_image_drop, pmhip_release and pmhip_destroy free it.  New functions and a new struct beside the others:
+ * PMHIP_ABI_VERSION stays 7.  A refused call returns PMHIP_E_ARG with the reason in pmhip_last_error and leaves the engine and the store as they were. */
+/* The working size of a W0 x H0 image: TImage::computeMaxResolution (Types.inl:2459-2477) with OPTDENSE::nResolutionLevel / nMinResolution / nMaxResolution, then
+ * Image::ResizeImage's size rule (double arithmetic, round half to even).  Needs no engine. */
+int pmhip_working_size(int W0, int H0, unsigned nResolutionLevel, unsigned nMinResolution, unsigned nMaxResolution, int* w, int* h);
+/* DepthData::ViewData::NeedScaleImage / ScaleImage's size: returns 0 when fabsf(scale - 1.f) < 0.15f (in float: the image is used as it is), else 1 with
+ * w, h = rint(W * scale), rint(H * scale). */
+int pmhip_scaled_size(int W, int H, float scale, int* w, int* h);
+/* Entry `key` (any int >= 0; a repeated key replaces the entry) gets the BGR u8 and gray f32 images at w x h of the decoded image img: W0*H0*3 bytes, host pointer,
+ * channelOrder 0 = B,G,R, 1 = R,G,B.  w == W0 and h == H0 only converts; enlarging (w > W0 or h > H0) is refused.  Blocking: img may be freed on return. */
+int pmhip_image_prepare(pmhip_engine* e, int key, const unsigned char* img, int W0, int H0, int channelOrder, int w, int h);
+/* Entry `key` gets ScaleImage(gray of entry srcKey, scale), gray only; w, h (nullable) receive its size.  A scale within 15 % of 1 is refused. */
+int pmhip_image_scale(pmhip_engine* e, int key, int srcKey, float scale, int* w, int* h);
+/* Download an entry: its size, gray (w*h floats), bgr (w*h*3 bytes); any pointer may be NULL, bgr must be NULL for a gray-only entry. */
+int pmhip_image_get(pmhip_engine* e, int key, int* w, int* h, float* gray, unsigned char* bgr);
+/* Free an entry; key < 0: all of them.  The store's working buffers (staging, tables) go with the last entry. */
+int pmhip_image_drop(pmhip_engine* e, int key);
+/* Device memory the store holds right now: entries, the staging of the last decoded image, the uploaded tables. */
+uint64_t pmhip_image_bytes(pmhip_engine* e);
+/* Since the engine was created or the last reset: images prepared and resampled, bytes of decoded images uploaded, the kernels' time by HIP events and the
+ * uploads' time on the host clock (each upload is waited for). */
+typedef struct PMHipImageStats {
+	uint64_t nPrepared, nScaled, bytesUploaded;
+	double kernelMs, uploadMs;
+} PMHipImageStats;
+int pmhip_image_stats_get(pmhip_engine* e, PMHipImageStats* out, int reset);
+/* pmhip_scene_set_view (the entry has the scene's size) or pmhip_scene_set_view_sized (any other size) with the stored gray image of entry `key`, read on the
+ * device, and pmhip_scene_set_color when the entry has a colour image.  The view holds copies: the entry may be dropped afterwards. */
+int pmhip_scene_set_view_stored(pmhip_engine* e, int idx, int key, const double K[9], const double R[9], const double C[3],
+                                float dMin, float dMax, const int32_t* neighbors, int nNeighbors);
 /* Device memory the resident scene holds right now, in bytes (images with their layouts, maps, masks, filter staging, batch scratch; not the fusion's working buffers). */
 uint64_t pmhip_scene_bytes(pmhip_engine* e);
 int pmhip_sync(pmhip_engine* e);

@@ -12,6 +12,7 @@
 #include "pm_fuse.hip"
 #include "pm_cloud.hip"
 #include "pm_cloud_filter.hip"
+#include "pm_image.hip"
 #include "hip_buf.h"
 #include <math.h>
 #include <stdio.h>
@@ -184,8 +185,23 @@ struct SceneMem {
 	DevBuf<PMUpTask> d_ups; PinBuf<PMUpTask> h_ups;     // [4][batchCap]
 };
 
+// The image store (pm_host_image.hip): working-resolution images made on the device from decoded 8-bit images, by caller-chosen key.  Independent of the scene -- images
+// are prepared before the scene's slot count is known, so pmhip_scene_create leaves it alone; pmhip_image_drop, pmhip_release and pmhip_destroy free it.
+struct ImgEntry { int w = 0, h = 0; DevBuf<uint8_t> bgr; DevBuf<float> gray; };   // bgr: w*h*3 or none (a resampled copy is gray only)
+struct ImageStore {
+	struct AreaTab { DevBuf<int> ofs, si; DevBuf<float> al; };
+	struct CubicTab { DevBuf<int> idx; DevBuf<float> c; };
+	std::map<int, ImgEntry> entries;
+	DevBuf<uint8_t> src;                          // staging of the decoded image (grow only)
+	AreaTab u8x, u8y, fx, fy; CubicTab cx, cy;    // the uploaded tables (grow only); the 8-bit resize keeps its pair while the sizes repeat
+	PMImgTab u8tx{}, u8ty{}; int u8Key[4] = {0, 0, 0, 0};
+	PMHipImageStats stats{};
+};
+
 struct pmhip_engine : SceneMem {
 	int device = 0;
+	ImageStore img;
+	hipEvent_t imgEv[2] = {nullptr, nullptr};     // bracket every kernel of the store (PMHipImageStats::kernelMs)
 	hipStream_t stream = nullptr;
 	// view groups of a batch sweep on their own streams so that the tail of one group's diagonal launch
 	// overlaps the next launch of another group (views are independent; diagonals of one view are not)
@@ -227,6 +243,14 @@ struct pmhip_engine : SceneMem {
 static void freeScene(pmhip_engine* e) {
 	hipSetDevice(e->device);
 	static_cast<SceneMem&>(*e) = SceneMem{};
+}
+
+// ... and every buffer of the image store here (its statistics stay)
+static void freeImages(pmhip_engine* e) {
+	hipSetDevice(e->device);
+	const PMHipImageStats kept = e->img.stats;
+	e->img = ImageStore{};
+	e->img.stats = kept;
 }
 
 #include "pm_host_estimate.hip"
@@ -279,6 +303,8 @@ void pmhip_destroy(pmhip_engine* e) {
 	if (e->stream) hipStreamSynchronize(e->stream);
 	for (auto& ev : e->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
 	freeScene(e);
+	freeImages(e);
+	for (hipEvent_t ev : e->imgEv) if (ev) hipEventDestroy(ev);
 	for (int g = 0; g < 16; ++g) { if (e->gstream[g]) hipStreamDestroy(e->gstream[g]); if (e->joinEv[g]) hipEventDestroy(e->joinEv[g]); }
 	if (e->forkEv) hipEventDestroy(e->forkEv);
 	if (e->stream) hipStreamDestroy(e->stream);
@@ -296,6 +322,7 @@ int pmhip_release(pmhip_engine* e) {
 	hipSetDevice(e->device);
 	hipStreamSynchronize(e->stream);
 	freeScene(e);
+	freeImages(e);
 	e->inited = false;
 	return 0;
 }
@@ -762,3 +789,4 @@ int pmhip_resize(pmhip_engine* e, int kind, const float* src, int w, int h, int 
 #include "pm_host_filter.hip"
 #include "pm_host_fuse.hip"
 #include "pm_host_cloud.hip"
+#include "pm_host_image.hip"

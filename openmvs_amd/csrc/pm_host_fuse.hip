@@ -29,7 +29,8 @@ static int ensureFuse(pmhip_engine* e) {
 
 extern "C" {
 
-int pmhip_scene_set_color(pmhip_engine* e, int idx, const unsigned char* bgr) {
+// pmhip_scene_set_color from a host image, or from a device image of the store (pmhip_scene_set_view_stored)
+static int sceneSetColor(pmhip_engine* e, int idx, const unsigned char* bgr, hipMemcpyKind kind) {
 	if (!e || !bgr || idx < 0 || idx >= e->nImages) return PMHIP_E_ARG;
 	HIPCHK(e, hipSetDevice(e->device));
 	auto& f = e->fu;
@@ -38,17 +39,18 @@ int pmhip_scene_set_color(pmhip_engine* e, int idx, const unsigned char* bgr) {
 	SceneView& v = e->views[idx];
 	if (v.sw) {                                                                  // a view with its own size keeps its colour image itself
 		if (!v.oBgr) HIPCHK(e, v.oBgr.alloc(3 * e->vpix(idx)));
-		HIPCHK(e, hipMemcpyAsync(v.oBgr, bgr, 3 * e->vpix(idx), hipMemcpyHostToDevice, e->stream));
+		HIPCHK(e, hipMemcpyAsync(v.oBgr, bgr, 3 * e->vpix(idx), kind, e->stream));
 		HIPCHK(e, hipStreamSynchronize(e->stream));
 		f.hasBgr[idx] = 1;
 		return 0;
 	}
 	if (!f.bgr) HIPCHK(e, f.bgr.alloc(3 * P * e->nImages));
-	HIPCHK(e, hipMemcpyAsync(f.bgr + 3 * P * idx, bgr, 3 * P, hipMemcpyHostToDevice, e->stream));
+	HIPCHK(e, hipMemcpyAsync(f.bgr + 3 * P * idx, bgr, 3 * P, kind, e->stream));
 	HIPCHK(e, hipStreamSynchronize(e->stream));
 	f.hasBgr[idx] = 1;
 	return 0;
 }
+int pmhip_scene_set_color(pmhip_engine* e, int idx, const unsigned char* bgr) { return sceneSetColor(e, idx, bgr, hipMemcpyHostToDevice); }
 
 int pmhip_scene_fuse(pmhip_engine* e, const int32_t* order, int nOrder, const PMHipFuseParams* prm, uint64_t* nPoints, uint64_t* nViews, uint64_t* nDepths) {
 	if (!e || !order || nOrder <= 0 || !prm || e->nImages < 1) return PMHIP_E_ARG;

@@ -126,6 +126,7 @@ class SceneViews:
         self.bgr = []                               # the colour images at the working resolution (B, G, R), for the fused cloud's colours
         self.all_view_scores = {}                   # image -> its WHOLE scored neighbour list (Image::neighbors: fusion order, and what a dense archive stores)
         self.avg_depth = {}                         # image -> average depth of its sparse points (Image::avgDepth)
+        self.stored = {}                            # slot -> key of the engine's image store that holds its images (load_scene(..., engine=...): `gray` / `bgr` are None there)
 
     @property
     def n_views(self):
@@ -301,7 +302,7 @@ def scale_image(gray, scale):
     return _resize_cubic_f32(gray, w, h, 1.0 / s) if s > 1 else _resize_area_f32(gray, w, h, 1.0 / s)
 
 
-def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=None, ignore_mask_label=None, mask_path=None, mask_loader=None):
+def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=None, ignore_mask_label=None, mask_path=None, mask_loader=None, engine=None):
     """Reads an MVSI scene and its images and runs view selection + depth initialisation for every valid image.
 
     `opt`: a `views.DenseOptions` or the whole option table (`optdense.OptDense`, e.g. from `optdense.load(<--dense-config-file>)`).
@@ -311,7 +312,11 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
     `DepthEstimator::ImportIgnoreMask` does (the scene's mask name, else <image>.mask.png; `mask_path` = `--mask-path`), read by `mask_loader(path) -> (h,w) labels`
     (default PIL), brought to the working resolution with INTER_NEAREST, and lands in `SceneViews.masks[i]` (1 = process, 0 = ignore) for `scene_set_mask`; an image
     whose mask cannot be read has none, as there (a warning in the reference), but `SceneViews.mask_option` tells the engine that the option is on (SceneDensify.cpp:661).
-    `image_loader(path) -> (h,w,3) uint8 RGB` defaults to PIL.  Returns a `SceneViews`."""
+    `image_loader(path) -> (h,w,3) uint8 RGB` defaults to PIL.
+    `engine` (a `PatchMatchHIP`): the images are prepared on the device.  Every decoded image goes straight to the engine's image store (`image_prepare`, key = its
+    slot; one decoded image in host memory at a time), every resampled copy is made there (`image_scale`); `SceneViews.gray[i]` / `.bgr[i]` are None and
+    `SceneViews.stored` = {slot: key} tells `PatchMatchHIP.scene_load` where the images are.  Sizes, view selection, seed maps and masks are the same (they never
+    read pixels), and so are the images, bit for bit.  Returns a `SceneViews`."""
     import numpy as np
     from . import mvsi, views
     opt = opt or views.DenseOptions()
@@ -336,7 +341,10 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
         H, W = rgb.shape[:2]
         res, _ = views.compute_max_resolution(W, H, opt.nResolutionLevel, opt.nMinResolution, opt.nMaxResolution)
         w, h = views.resized_size(W, H, res)
-        if (w, h) != (W, H):
+        if engine is not None:
+            engine.image_prepare(len(sizes), rgb, w, h, channel_order=1); sv.stored[len(sizes)] = len(sizes)
+            rgb = None
+        elif (w, h) != (W, H):
             rgb = _resize_area_u8(rgb, w, h)
         rgbs.append(rgb); sizes.append((w, h))
     sv.width, sv.height = max(set(sizes), key=lambda wh: (sizes.count(wh), -sizes.index(wh)))     # the scene's size: the most frequent one; the other images carry their own
@@ -360,8 +368,8 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
             sv.masks[i] = views.import_ignore_mask(labels, sizes[i], ignore_mask_label)
     cams = views.Cameras(sc, sizes)
     for i, im in enumerate(sc.images):
-        sv.gray.append(views.to_gray(rgbs[i])); sv.names.append(im.name)
-        sv.bgr.append(np.ascontiguousarray(rgbs[i][..., ::-1]))
+        sv.gray.append(None if rgbs[i] is None else views.to_gray(rgbs[i])); sv.names.append(im.name)
+        sv.bgr.append(None if rgbs[i] is None else np.ascontiguousarray(rgbs[i][..., ::-1]))
         sv.K.append(cams.K[i]); sv.R.append(cams.R[i]); sv.C.append(cams.C[i])
         whole = []
         sel = views.select_views(sc, cams, i, opt, all_neighbors=whole) if im.is_valid() else None
@@ -388,8 +396,11 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
                 continue
             key = (j, float(scale))
             if key not in made:
-                img = scale_image(sv.gray[j], scale)
-                Kj, Rj, Cj, w, h = sc.camera(j, (img.shape[1], img.shape[0]))          # Image::GetCamera(platforms, image.size())
+                if engine is not None:
+                    img, size = None, engine.image_scale(len(sv.gray), sv.stored[j], scale); sv.stored[len(sv.gray)] = len(sv.gray)
+                else:
+                    img = scale_image(sv.gray[j], scale); size = (img.shape[1], img.shape[0])
+                Kj, Rj, Cj, w, h = sc.camera(j, size)          # Image::GetCamera(platforms, image.size())
                 made[key] = len(sv.gray)
                 sv.alias_of[made[key]] = j
                 sv.gray.append(img); sv.K.append(Kj); sv.R.append(Rj); sv.C.append(Cj); sv.sizes.append((w, h)); sv.names.append(sv.names[j])
@@ -419,7 +430,8 @@ def fuse_depth_maps(engine, scene, opt=None, bgr=None) -> dict:
     want_color = colors == 2 and bgr is not None
     if want_color:
         for i in range(len(scene.gray) - len(scene.alias_of)):
-            engine.scene_set_color(i, bgr[i])
+            if bgr[i] is not None:                                    # (None: the colour image came with the view from the image store)
+                engine.scene_set_color(i, bgr[i])
     return engine.scene_fuse(fuse_order(scene), n_min, f_depth, f_normal, want_color, normals == 2)
 
 
@@ -443,7 +455,8 @@ def finish_point_cloud(engine, scene_or_archive, opt, crop_to_roi: bool = False,
         if views is None:
             raise ValueError("finish_point_cloud: colours need the SceneViews with the images")
         for i in range(len(views.gray) - len(getattr(views, "alias_of", {}))):
-            engine.scene_set_color(i, views.bgr[i])
+            if views.bgr[i] is not None:
+                engine.scene_set_color(i, views.bgr[i])
     out = engine.scene_cloud_finish(crop_obb=obb, border_roi=float(border_roi), estimate_colors=colors, estimate_normals=normals)
     out.setdefault("nDepths", (cloud or {}).get("nDepths", 0))
     if cloud is not None and "rounds" in cloud:
@@ -516,7 +529,7 @@ def filter_point_cloud(engine, mvs_in: str, mvs_out: str | None = None, th_remov
 
 
 def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None,
-                         crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, **load_args):
+                         crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, prepare_on_device: bool = False, **load_args):
     """`Scene::DenseReconstruction(nFusionMode)` (libs/MVS/SceneDensify.cpp:1655-1750) for the PatchMatch path on one engine: prepare the views (`load_scene`), estimate all
     depth maps with the geometric rounds and the filters the option table asks for (`compute_depth_maps`; with `dmap_dir` under the reference's file contract), and -- unless
     `fusion_mode` is 1, "export depth maps only" -- fuse them and write `<scene>_dense.mvs` to `mvs_out`.  `opt`: an `optdense.OptDense` (default: the table's defaults with the
@@ -524,6 +537,8 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     view_neighbors_file, ignore_mask_label, mask_path, mask_loader).  The SGM modes (-1, -2) are openmvs_amd.sgm_pipeline's.  After the fusion the cloud is finished
     (`finish_point_cloud`): `crop_to_roi` / `border_roi` as the application's `--crop-to-roi` (default 1 there, off here) / `--border-roi`, colours and normals of modes 1.
     `filter_point_cloud` < 0: `Scene::PointCloudFilter` with that threshold on the finished cloud (`PatchMatchHIP.scene_cloud_filter`; default 0: off).
+    `prepare_on_device`: the decoded images are resized, converted and resampled on the engine (`load_scene(..., engine=engine)`) -- the same depth maps and cloud, but the
+    returned `SceneViews` has no host images (`gray[i]` / `bgr[i]` are None), which is why it is off by default.
     Returns (SceneViews, cloud or None)."""
     from . import optdense
     th_filter = int(filter_point_cloud)
@@ -531,7 +546,7 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
         raise ValueError("fusion_mode %d: the PatchMatch path is modes 0 (estimate + fuse) and 1 (depth maps only)" % fusion_mode)
     if opt is None:
         opt = optdense.defaults(); opt.nNumViews = 8; opt.nEstimateNormals = 2
-    sv = load_scene(mvs_in, opt=opt, **load_args)
+    sv = load_scene(mvs_in, opt=opt, engine=engine if prepare_on_device else None, **load_args)
     engine.scene_load(sv, n_levels=int(opt.nSubResolutionLevels))
     compute_depth_maps(engine, sv.ids, opt.params(seed), n_optimize=int(opt.nOptimize), b_filter_adjust=bool(opt.bFilterAdjust), n_speckle_size=int(opt.nSpeckleSize),
                        n_ipol_gap_size=int(opt.nIpolGapSize), f_depth_diff_threshold=float(opt.fDepthDiffThreshold), n_min_views_filter=int(opt.nMinViewsFilter),

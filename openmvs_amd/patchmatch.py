@@ -61,6 +61,10 @@ class PMHipCloudFilterParams(C.Structure):
                 ("camC", C.POINTER(C.c_double)), ("camAngle", C.POINTER(C.c_float))]
 
 
+class PMHipImageStats(C.Structure):
+    _fields_ = [("nPrepared", C.c_uint64), ("nScaled", C.c_uint64), ("bytesUploaded", C.c_uint64), ("kernelMs", C.c_double), ("uploadMs", C.c_double)]
+
+
 PMHIP_ABI_VERSION = 7      # include/pmhip.h
 
 
@@ -68,7 +72,8 @@ class PMHipTuning(C.Structure):
     _fields_ = [("viewGroups", C.c_int32), ("wideMaxViews", C.c_int32), ("wideHyps", C.c_int32), ("sweepLanes", C.c_int32), ("quadBuffer", C.c_int32), ("widePixels", C.c_int32), ("wide8Pixels", C.c_int32), ("reserved0", C.c_int32)]
 
 
-EXPORTS = ["pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_scene_cloud_finish", "pmhip_scene_cloud_set", "pmhip_scene_cloud_knn", "pmhip_scene_cloud_times", "pmhip_scene_cloud_load", "pmhip_scene_cloud_filter", "pmhip_scene_cloud_visibility", "pmhip_scene_cloud_filter_cones", "pmhip_scene_cloud_filter_times", "pmhip_scene_cloud_filter_counts", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
+EXPORTS = ["pmhip_working_size", "pmhip_scaled_size", "pmhip_image_prepare", "pmhip_image_scale", "pmhip_image_get", "pmhip_image_drop", "pmhip_image_bytes", "pmhip_image_stats_get", "pmhip_scene_set_view_stored",
+           "pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_scene_cloud_finish", "pmhip_scene_cloud_set", "pmhip_scene_cloud_knn", "pmhip_scene_cloud_times", "pmhip_scene_cloud_load", "pmhip_scene_cloud_filter", "pmhip_scene_cloud_visibility", "pmhip_scene_cloud_filter_cones", "pmhip_scene_cloud_filter_times", "pmhip_scene_cloud_filter_counts", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
            "pmhip_estimate_depth_map", "pmhip_estimate_depth_map_masked", "pmhip_last_error", "pmhip_scene_create", "pmhip_scene_set_view",
            "pmhip_scene_estimate", "pmhip_scene_commit_round", "pmhip_scene_reset_view", "pmhip_scene_set_maps",
            "pmhip_scene_get_maps", "pmhip_scene_device_ptr", "pmhip_scene_copy", "pmhip_scene_filter", "pmhip_scene_filter_commit", "pmhip_scene_gap_interpolation", "pmhip_scene_remove_small_segments", "pmhip_scene_images_updated", "pmhip_scene_maps_updated", "pmhip_scene_bytes", "pmhip_sync",
@@ -93,9 +98,11 @@ def load_library() -> C.CDLL:
         lib.pmhip_stream.restype = C.c_void_p
         lib.pmhip_destroy.restype = None
         lib.pmhip_scene_fuse_rounds.restype = C.c_uint64
+        if hasattr(lib, "pmhip_image_bytes"):
+            lib.pmhip_image_bytes.restype = C.c_uint64
         experiment = bool(os.environ.get("PMHIP_LIB"))        # (an older build of the library in an A/B run may lack the newest entry points)
         for n in EXPORTS:
-            if not (experiment and n in ("pmhip_set_sweep_tiles", "pmhip_abi_version")):
+            if not (experiment and (n in ("pmhip_set_sweep_tiles", "pmhip_abi_version", "pmhip_working_size", "pmhip_scaled_size", "pmhip_scene_set_view_stored") or n.startswith("pmhip_image_"))):
                 getattr(lib, n)  # raises AttributeError if a declared symbol is missing
         if hasattr(lib, "pmhip_abi_version"):
             lib.pmhip_abi_version.restype = C.c_uint32
@@ -111,6 +118,21 @@ def default_params(**kw) -> PMHipParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def working_size(W0: int, H0: int, n_resolution_level: int = 1, n_min_resolution: int = 640, n_max_resolution: int = 0):
+    """pmhip_working_size: the (w, h) an image of W0 x H0 is brought to (`views.compute_max_resolution` + `views.resized_size`).  Needs no device."""
+    w, h = C.c_int(), C.c_int()
+    rc = load_library().pmhip_working_size(int(W0), int(H0), C.c_uint(int(n_resolution_level)), C.c_uint(int(n_min_resolution)), C.c_uint(int(n_max_resolution)), C.byref(w), C.byref(h))
+    if rc != 0:
+        raise ValueError("pmhip_working_size(%d, %d): error %d" % (W0, H0, rc))
+    return w.value, h.value
+
+
+def scaled_size(W: int, H: int, scale):
+    """pmhip_scaled_size: the (w, h) of `ScaleImage(scale)` of a W x H image, or None when `NeedScaleImage` is false.  Needs no device."""
+    w, h = C.c_int(), C.c_int()
+    return (w.value, h.value) if load_library().pmhip_scaled_size(int(W), int(H), C.c_float(float(np.float32(scale))), C.byref(w), C.byref(h)) else None
 
 
 def _fp(a):
@@ -233,14 +255,22 @@ class PatchMatchHIP:
         """The identity slot idx draws its random numbers under (pmhip_scene_set_view_id): the view's index in the whole scene when this engine holds a part of it."""
         self._chk(self._lib.pmhip_scene_set_view_id(self._h, int(idx), C.c_uint32(int(view_id))))
 
-    def scene_load(self, scene, n_levels=2):
-        """Upload a synth.Scene (or anything with the same attributes)."""
+    def scene_load(self, scene, n_levels=2, drop_stored=True):
+        """Upload a synth.Scene (or anything with the same attributes).  Slots listed in `scene.stored` ({slot: key}; densify.load_scene(..., engine=self)) adopt their
+        images from the image store on the device (scene_set_view_stored); `drop_stored`: the entries are dropped afterwards."""
         self.scene_create(scene.n_views, scene.width, scene.height, n_levels)
         sizes = getattr(scene, "sizes", None) or []
+        stored = getattr(scene, "stored", None) or {}
         nbs = getattr(scene, "estimate_neighbors", None) or scene.neighbors       # (a densify.SceneViews lists resampled copies of neighbours here, ViewData::ScaleImage)
         for i in range(scene.n_views):
+            if i in stored:
+                self.scene_set_view_stored(i, stored[i], scene.K[i], scene.R[i], scene.C[i], float(scene.dmin[i]), float(scene.dmax[i]), nbs[i])
+                continue
             own = i < len(sizes) and tuple(sizes[i]) != (scene.width, scene.height)
             (self.scene_set_view_sized if own else self.scene_set_view)(i, scene.gray[i], scene.K[i], scene.R[i], scene.C[i], float(scene.dmin[i]), float(scene.dmax[i]), nbs[i])
+        if drop_stored:
+            for k in sorted(set(stored.values())):
+                self.image_drop(k)
         # ignore masks of a scene loaded with --ignore-mask-label (densify.load_scene): per image where a mask file was found; the option alone already selects the
         # nearest-neighbour level hand-off (SceneDensify.cpp:661)
         for i, m in getattr(scene, "masks", {}).items():
@@ -255,6 +285,68 @@ class PatchMatchHIP:
         nb = np.ascontiguousarray(neighbors, np.int32)
         self._chk(self._lib.pmhip_scene_set_view_sized(self._h, idx, _fp(g), g.shape[1], g.shape[0], 0, _dp(K), _dp(R), _dp(Cc), C.c_float(dmin), C.c_float(dmax),
                                                        nb.ctypes.data_as(C.POINTER(C.c_int32)), len(nb)))
+
+    # -- the image store: working-resolution images made on the device (include/pmhip.h, section 2b) ---------------------------------
+    def image_prepare(self, key, img, w, h, channel_order=1):
+        """Entry `key` of the image store gets the BGR u8 and gray f32 images at w x h of the decoded (H0, W0, 3) uint8 image `img` (pmhip_image_prepare: INTER_AREA as
+        `densify._resize_area_u8`, gray as `views.to_gray`).  channel_order: 0 = the array is B, G, R; 1 = R, G, B."""
+        a = np.ascontiguousarray(img, np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("img must be (h, w, 3) uint8")
+        self._chk(self._lib.pmhip_image_prepare(self._h, int(key), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], int(channel_order), int(w), int(h)))
+        self._images = getattr(self, "_images", {}); self._images[int(key)] = (int(w), int(h), True)
+
+    def image_scale(self, key, src_key, scale):
+        """Entry `key` gets `ScaleImage(gray of entry src_key, scale)`, gray only (pmhip_image_scale: `densify.scale_image`); returns its (w, h)."""
+        w, h = C.c_int(), C.c_int()
+        self._chk(self._lib.pmhip_image_scale(self._h, int(key), int(src_key), C.c_float(float(np.float32(scale))), C.byref(w), C.byref(h)))
+        self._images = getattr(self, "_images", {}); self._images[int(key)] = (w.value, h.value, False)
+        return w.value, h.value
+
+    def image_get(self, key):
+        """(gray (h, w) float32, bgr (h, w, 3) uint8 or None for a gray-only entry) of entry `key` (pmhip_image_get)."""
+        w, h = C.c_int(), C.c_int()
+        self._chk(self._lib.pmhip_image_get(self._h, int(key), C.byref(w), C.byref(h), None, None))
+        gray = np.zeros((h.value, w.value), np.float32)
+        self._chk(self._lib.pmhip_image_get(self._h, int(key), None, None, _fp(gray), None))
+        bgr = np.zeros((h.value, w.value, 3), np.uint8)
+        if self._lib.pmhip_image_get(self._h, int(key), None, None, None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
+            bgr = None
+        return gray, bgr
+
+    def image_drop(self, key=-1):
+        """Free entry `key` of the image store; key < 0: everything (pmhip_image_drop)."""
+        self._chk(self._lib.pmhip_image_drop(self._h, int(key)))
+        if int(key) < 0:
+            self._images = {}
+        else:
+            getattr(self, "_images", {}).pop(int(key), None)
+
+    def image_bytes(self) -> int:
+        """Device memory the image store holds right now (pmhip_image_bytes)."""
+        return int(self._lib.pmhip_image_bytes(self._h))
+
+    def image_stats(self, reset=False) -> dict:
+        """pmhip_image_stats_get: images prepared / resampled, bytes of decoded images uploaded, kernel time by HIP events and upload time, in ms."""
+        s = PMHipImageStats()
+        self._chk(self._lib.pmhip_image_stats_get(self._h, C.byref(s), 1 if reset else 0))
+        return dict(prepared=int(s.nPrepared), scaled=int(s.nScaled), bytes_uploaded=int(s.bytesUploaded), kernel_ms=float(s.kernelMs), upload_ms=float(s.uploadMs))
+
+    def scene_set_view_stored(self, idx, key, K, R, Cc, dmin, dmax, neighbors):
+        """scene_set_view / scene_set_view_sized (by the entry's size) with the stored gray image of entry `key`, read on the device, and its colour image if it has one
+        (pmhip_scene_set_view_stored).  The view holds copies."""
+        nb = np.ascontiguousarray(neighbors, np.int32)
+        self._chk(self._lib.pmhip_scene_set_view_stored(self._h, int(idx), int(key), _dp(K), _dp(R), _dp(Cc), C.c_float(dmin), C.c_float(dmax),
+                                                        nb.ctypes.data_as(C.POINTER(C.c_int32)), len(nb)))
+        w, h, _ = getattr(self, "_images", {}).get(int(key), (None, None, False))
+        if w is None:                                          # (an entry made through the C ABI directly)
+            cw, ch = C.c_int(), C.c_int()
+            self._chk(self._lib.pmhip_image_get(self._h, int(key), C.byref(cw), C.byref(ch), None, None)); w, h = cw.value, ch.value
+        self._sizes = getattr(self, "_sizes", {})
+        if (w, h) == tuple(self._scene[1:]):
+            self._sizes.pop(int(idx), None)
+        else:
+            self._sizes[int(idx)] = (w, h)
 
     def scene_set_source_depth(self, idx, depth, Kd=None, Rd=None, Cd=None):
         """Known depth map of a source view with the camera stored next to it (pmhip_scene_set_source_depth); depth None removes it."""
