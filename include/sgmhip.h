@@ -9,6 +9,7 @@
  * SceneDensify.cpp:2048).  Those members become plain arguments here; everything around the call
  * (rectification, pyramid, range maps, cross-check, sub-pixel refinement) stays with the caller.
  * Integer outputs are bit-identical to the reference algorithm (u8 costs, u16 sums, i16 disparities).
+ * The library reads no environment variable: its kernels are chosen by the problem and by sgmhip_set_sub_group_kernels.
  */
 #ifndef SGMHIP_H_
 #define SGMHIP_H_

@@ -17,7 +17,7 @@
 struct SGMProblemBufs {   // buffers of the resident problem and what they hold: grown together, never shrunk (sgmReserve)
 	size_t capImg = 0, capPix = 0, capCosts = 0;
 	DevBuf<unsigned char> d_color; DevBuf<float> d_grayL, d_grayR;
-	DevBuf<SGMPixel> d_pixels; DevBuf<unsigned char> d_costs; DevBuf<unsigned short> d_accums; DevBuf<float4> d_setup;
+	DevBuf<SGMPixel> d_pixels; DevBuf<unsigned char> d_costs; DevBuf<unsigned short> d_accums;
 	DevBuf<short> d_disp; DevBuf<unsigned short> d_cost;
 };
 struct sgmhip_engine : SGMProblemBufs {
@@ -58,7 +58,7 @@ static int sgmReserve(sgmhip_engine* e, int w, int h, uint64_t numCosts, int max
 		const size_t cI = std::max(nImg, e->capImg), cP = std::max(nPix, e->capPix), cC = std::max<size_t>(numCosts, e->capCosts);
 		sgmFree(e);
 		SGMCHK(e, e->d_color.alloc(cI * 3)); SGMCHK(e, e->d_grayL.alloc(cI)); SGMCHK(e, e->d_grayR.alloc(cI));
-		SGMCHK(e, e->d_pixels.alloc(cP)); SGMCHK(e, e->d_disp.alloc(cP)); SGMCHK(e, e->d_cost.alloc(cP)); SGMCHK(e, e->d_setup.alloc(cP));
+		SGMCHK(e, e->d_pixels.alloc(cP)); SGMCHK(e, e->d_disp.alloc(cP)); SGMCHK(e, e->d_cost.alloc(cP));
 		SGMCHK(e, e->d_costs.alloc(cC + 256)); SGMCHK(e, e->d_accums.alloc((cC + 3) / 4 * 4 + 4)); // u16 sums, addressed as 32-bit words by the path kernels
 		e->capImg = cI; e->capPix = cP; e->capCosts = cC;
 	}
@@ -106,29 +106,23 @@ int sgmhip_set_problem(sgmhip_engine* e, const uint8_t* leftBGR, const float* le
 	SGMCHK(e, hipMemcpyAsync(e->d_grayL, leftGray, nImg * 4, hipMemcpyHostToDevice, e->stream));
 	SGMCHK(e, hipMemcpyAsync(e->d_grayR, rightGray, nImg * 4, hipMemcpyHostToDevice, e->stream));
 	SGMCHK(e, hipMemcpyAsync(e->d_pixels, pixels, nPix * sizeof(SGMPixel), hipMemcpyHostToDevice, e->stream));
-	// one range for all pixels?  (then Match aggregates with sgm_path_uniform_kernel)
-	static const bool allowUniform = [] { const char* v = getenv("SGMHIP_UNIFORM"); return !v || atoi(v) != 0; }();
+	// one range for all pixels?  (then Match takes the strip cost kernel and aggregates with sgm_path_uniform_kernel)
 	SGMUniform hu = {1, 0, 0, 0};
-	if (allowUniform) {
-		if (!e->d_uniform) SGMCHK(e, e->d_uniform.alloc(1));
-		SGMCHK(e, hipMemcpyAsync(e->d_uniform, &hu, sizeof(hu), hipMemcpyHostToDevice, e->stream));
-		hipLaunchKernelGGL(sgm_uniform_check_kernel, dim3((unsigned)((nPix + 255) / 256)), dim3(256), 0, e->stream, e->d_pixels, (long)nPix, e->d_uniform);
-		SGMCHK(e, hipMemcpyAsync(&hu, e->d_uniform, sizeof(hu), hipMemcpyDeviceToHost, e->stream));
-	} else hu.ok = 0;
+	if (!e->d_uniform) SGMCHK(e, e->d_uniform.alloc(1));
+	SGMCHK(e, hipMemcpyAsync(e->d_uniform, &hu, sizeof(hu), hipMemcpyHostToDevice, e->stream));
+	hipLaunchKernelGGL(sgm_uniform_check_kernel, dim3((unsigned)((nPix + 255) / 256)), dim3(256), 0, e->stream, e->d_pixels, (long)nPix, e->d_uniform);
+	SGMCHK(e, hipMemcpyAsync(&hu, e->d_uniform, sizeof(hu), hipMemcpyDeviceToHost, e->stream));
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	e->uniform = hu.ok != 0 && hu.maxDisp - hu.minDisp == maxNumDisp && (uint64_t)nPix * (uint64_t)maxNumDisp == numCosts;
 	e->uniformMin = hu.minDisp; e->uniformMax = hu.maxDisp;
 	return 0;
 }
 
-static void launchPath(sgmhip_engine* e, hipStream_t st, int NK, int lines, int P1, const SGMDirs& dirs, bool delta) {
-#define SGM_LAUNCH_PATH(NK_, DL_) hipLaunchKernelGGL((sgm_path_kernel<NK_, DL_>), dim3(lines), dim3(64), 0, st, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, P1, dirs, e->d_deltas, (unsigned long long)e->numCosts)
-	switch (NK) {
-	case 1: if (delta) SGM_LAUNCH_PATH(1, true); else SGM_LAUNCH_PATH(1, false); break;
-	case 2: if (delta) SGM_LAUNCH_PATH(2, true); else SGM_LAUNCH_PATH(2, false); break;
-	default: if (delta) SGM_LAUNCH_PATH(4, true); else SGM_LAUNCH_PATH(4, false); break;
-	}
-#undef SGM_LAUNCH_PATH
+// the penalty table of the next Match on the device, and its maximum (which decides between byte deltas and u16 atomic sums)
+static int sgmSetP2s(sgmhip_engine* e, const uint16_t P2s[256]) {
+	SGMCHK(e, hipMemcpyAsync(e->d_P2s, P2s, 512, hipMemcpyHostToDevice, e->stream));
+	e->maxP2 = *std::max_element(P2s, P2s + 256);
+	return 0;
 }
 // the 8 byte volumes of the DELTA aggregation (kept between calls, grown on demand); false: no room, the caller takes the atomic path
 static bool ensureDeltas(sgmhip_engine* e) {
@@ -140,119 +134,10 @@ static bool ensureDeltas(sgmhip_engine* e) {
 	return false;
 }
 
-static int sgmMatch(sgmhip_engine* e, uint16_t P1);
-int sgmhip_match(sgmhip_engine* e, uint16_t P1, const uint16_t P2s[256], int sync) {
-	if (!e || !P2s || e->numCosts == 0) return SGMHIP_E_ARG;
-	SGMCHK(e, hipSetDevice(e->device));
-	SGMCHK(e, hipMemcpyAsync(e->d_P2s, P2s, 512, hipMemcpyHostToDevice, e->stream));
-	e->maxP2 = 0; for (int i = 0; i < 256; ++i) e->maxP2 = std::max(e->maxP2, (int)P2s[i]);
-	{ const int rc = sgmMatch(e, P1); if (rc) return rc; }
-	if (sync) SGMCHK(e, hipStreamSynchronize(e->stream));
-	return 0;
-}
-// cost volume, 8-path aggregation and winner-take-all of the resident problem (P2s already on the device), asynchronous on the engine's stream
-// sub-group variant: LP lanes per pixel / pair / line
-extern "C++" {
-template <int LP>
-static int sgmMatchSubT(sgmhip_engine* e, uint16_t P1) {
-	constexpr int PW = 64 / LP;
-	const long nPix = (long)e->vw * e->vh;
-	const int W = e->vw, H = e->vh;
-	evB(e, 0);
-	// cost volume: the lane-per-pixel kernel serves narrow ranges too (0.9 against 1.28 ms for 3-12 disparities per pixel at 2048x1536); SGMHIP_COST_PX=0: the sub-group kernel
-	static const bool pxCost = [] { const char* v = getenv("SGMHIP_COST_PX"); return !v || atoi(v) != 0; }();
-	if (pxCost) {
-		const long nTiles = (long)((W + 63) / 64) * H;
-		hipLaunchKernelGGL(sgm_cost_px_kernel, dim3((unsigned)((nTiles + 3) / 4)), dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->d_pixels, e->d_costs);
-	} else {
-		hipLaunchKernelGGL(sgm_setup_kernel, dim3((unsigned)((nPix + 255) / 256)), dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->w, W, H, e->d_pixels, e->d_setup);
-		const long nPairs = (long)((W + 1) / 2) * H;
-		hipLaunchKernelGGL((sgm_cost_sub_kernel<LP>), dim3((unsigned)((nPairs + 4 * PW - 1) / (4 * PW))), dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->d_pixels, e->d_setup, e->d_costs);
-	}
-	evE(e);
-	static const int allowDeltaSub = [] { const char* v = getenv("SGMHIP_DELTA"); return v ? atoi(v) : 3; }();
-	bool delta = e->maxP2 <= 255 && (allowDeltaSub & 2) != 0;
-	if (delta && !ensureDeltas(e)) delta = false;
-	if (!delta) SGMCHK(e, hipMemsetAsync(e->d_accums, 0, (e->numCosts + 1) / 2 * 4, e->stream));
-	struct Dir { int dx, dy; SGMLines ln; } dirs[8] = {
-		{0, 1,   {W, 0, 0, 1, 0,      0, 0, 0, 0, 0}},
-		{1, 0,   {H, 0, 0, 0, 1,      0, 0, 0, 0, 0}},
-		{0, -1,  {W, 0, H - 1, 1, 0,  0, 0, 0, 0, 0}},
-		{-1, 0,  {H, W - 1, 0, 0, 1,  0, 0, 0, 0, 0}},
-		{1, 1,   {W, 0, 0, 1, 0,      H - 1, 0, 1, 0, 1}},
-		{-1, 1,  {W - 1, 0, 0, 1, 0,  H, W - 1, 0, 0, 1}},
-		{1, -1,  {W - 1, 1, H - 1, 1, 0,  H, 0, 0, 0, 1}},
-		{-1, -1, {W, 0, H - 1, 1, 0,  H - 1, W - 1, 0, 0, 1}},
-	};
-	const int horizFirst[8] = {1, 3, 0, 2, 4, 5, 6, 7}, vertFirst[8] = {0, 2, 1, 3, 4, 5, 6, 7};
-	const int* ord = W >= H ? horizFirst : vertFirst;
-	SGMDirs sd; memset(&sd, 0, sizeof(sd));
-	int total = 0;                                                     // in workgroups: PW lines each
-	for (int i = 0; i < 8; ++i) {
-		const Dir& d = dirs[ord[i]];
-		sd.dx[i] = d.dx; sd.dy[i] = d.dy; sd.ln[i] = d.ln; sd.first[i] = total;
-		total += (d.ln.nA + d.ln.nB + PW - 1) / PW;
-	}
-	sd.first[8] = total;
-	evB(e, 1);
-	if (total > 0) {
-#define SGM_LAUNCH_SUB(MD_, DL_) hipLaunchKernelGGL((sgm_path_sub_kernel<LP, MD_, DL_>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
-		if (e->maxNumDisp <= 64) { if (delta) SGM_LAUNCH_SUB(64, true); else SGM_LAUNCH_SUB(64, false); }
-		else { if (delta) SGM_LAUNCH_SUB(256, true); else SGM_LAUNCH_SUB(256, false); }
-#undef SGM_LAUNCH_SUB
-	}
-	if (e->statsOn) e->stats.aggrLaunches += 1;
-	evE(e);
-	evB(e, 2);
-	if (delta) hipLaunchKernelGGL(sgm_sum_wta_kernel, dim3((unsigned)((nPix + 15) / 16)), dim3(256), 0, e->stream, e->d_pixels, e->d_costs, e->d_deltas, (unsigned long long)e->numCosts, e->d_accums, nPix, e->d_disp, e->d_cost);
-	else hipLaunchKernelGGL((sgm_wta_sub_kernel<LP>), dim3((unsigned)((nPix + 4 * PW - 1) / (4 * PW))), dim3(256), 0, e->stream, e->d_pixels, e->d_accums, nPix, e->d_disp, e->d_cost);
-	evE(e);
-	SGMCHK(e, hipGetLastError());
-	if (e->statsOn) e->stats.calls += 1;
-	return 0;
-}
-
-} // extern "C++"
-
-static int sgmMatchSub(sgmhip_engine* e, uint16_t P1) {
-	switch (e->subGroups) {
-	case 8: return sgmMatchSubT<8>(e, P1);
-	case 32: return sgmMatchSubT<32>(e, P1);
-	default: return sgmMatchSubT<16>(e, P1);
-	}
-}
-
-static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
-	if (e->subGroups) return sgmMatchSub(e, P1);
-	const long nPix = (long)e->vw * e->vh;
-	const int W = e->vw, H = e->vh;
-	evB(e, 0);
-	static const bool pxCost = [] { const char* v = getenv("SGMHIP_COST_PX"); return !v || atoi(v) != 0; }();   // 0: the wave-per-pixel-pair cost kernel
-	static const bool uniCost = [] { const char* v = getenv("SGMHIP_COST_UNI"); return !v || atoi(v) != 0; }();   // 0: the sliding-window kernel for uniform ranges too
-	if (pxCost) {
-		// one pixel per lane, 64-pixel tiles of a row per wave (does the left-window prologue itself); with one range for all pixels the right-image strip of a tile sits in LDS
-		const long nTiles = (long)((W + 63) / 64) * H;
-		const dim3 g((unsigned)((nTiles + 3) / 4));
-		if (e->uniform && uniCost) {
-#define SGM_LAUNCH_UNI(MD_) hipLaunchKernelGGL((sgm_cost_uni_kernel<MD_>), g, dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->uniformMin, e->maxNumDisp, e->d_costs)
-			if (e->maxNumDisp <= 64) SGM_LAUNCH_UNI(64); else if (e->maxNumDisp <= 128) SGM_LAUNCH_UNI(128); else SGM_LAUNCH_UNI(256);
-#undef SGM_LAUNCH_UNI
-		} else hipLaunchKernelGGL(sgm_cost_px_kernel, g, dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->d_pixels, e->d_costs);
-	} else {
-		hipLaunchKernelGGL(sgm_setup_kernel, dim3((unsigned)((nPix + 255) / 256)), dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->w, W, H, e->d_pixels, e->d_setup);
-		const long nPairs = (long)((W + 1) / 2) * H;
-		hipLaunchKernelGGL(sgm_cost_kernel, dim3((unsigned)((nPairs + 3) / 4)), dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->d_pixels, e->d_setup, e->d_costs);
-	}
-	evE(e);
-	const int NK = e->maxNumDisp <= 64 ? 1 : (e->maxNumDisp <= 128 ? 2 : 4);
-	// DELTA aggregation: penalties that fit a byte (L - C <= P2); 8 scratch bytes per entry.  Uniform ranges: the register-resident kernel (NK <= 2); ragged ranges
-	// (round 4): sgm_path_kernel<NK, true> -- one coalesced byte store per lane and step instead of an atomic add into the shared u16 sums
-	static const int allowDelta = [] { const char* v = getenv("SGMHIP_DELTA"); return v ? atoi(v) : 3; }();   // bit 0: uniform ranges, bit 1: ragged ranges; 0: atomic u16 sums
-	bool delta = e->maxP2 <= 255 && ((e->uniform && NK <= 2) ? (allowDelta & 1) != 0 : (allowDelta & 2) != 0);
-	if (delta && !ensureDeltas(e)) delta = false;   // no room: the atomic path
-	if (!delta) SGMCHK(e, hipMemsetAsync(e->d_accums, 0, (e->numCosts + 1) / 2 * 4, e->stream)); // imageAccumCosts.Memset(0), :990
-	// the eight paths with the threaded variant's start sets, SemiGlobalMatcher.cpp:1083-1200
-	struct Dir { int dx, dy; SGMLines ln; } dirs[8] = {
+// the eight paths with the threaded variant's start sets (SemiGlobalMatcher.cpp:1083-1200) as one grid, `linesPerGroup` lines to a workgroup
+// (first[] counts workgroups); -> the number of workgroups
+static int sgmSchedule(int W, int H, int linesPerGroup, SGMDirs& sd) {
+	const struct Dir { int dx, dy; SGMLines ln; } dirs[8] = {
 		{0, 1,   {W, 0, 0, 1, 0,      0, 0, 0, 0, 0}},            // width-down
 		{1, 0,   {H, 0, 0, 0, 1,      0, 0, 0, 0, 0}},            // height-right
 		{0, -1,  {W, 0, H - 1, 1, 0,  0, 0, 0, 0, 0}},            // width-up
@@ -262,55 +147,102 @@ static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
 		{1, -1,  {W - 1, 1, H - 1, 1, 0,  H, 0, 0, 0, 1}},        // right-up: bottom row x >= 1, then left column
 		{-1, -1, {W, 0, H - 1, 1, 0,  H - 1, W - 1, 0, 0, 1}},    // left-up: bottom row, then right column y <= H-2
 	};
-	// one grid for all of them, the directions with the longest lines first (their chains bound the kernel's duration)
+	// the directions with the longest lines first (their chains bound the kernel's duration)
 	const int horizFirst[8] = {1, 3, 0, 2, 4, 5, 6, 7}, vertFirst[8] = {0, 2, 1, 3, 4, 5, 6, 7};
 	const int* ord = W >= H ? horizFirst : vertFirst;
-	SGMDirs sd; memset(&sd, 0, sizeof(sd));
+	memset(&sd, 0, sizeof(sd));
 	int total = 0;
 	for (int i = 0; i < 8; ++i) {
 		const Dir& d = dirs[ord[i]];
 		sd.dx[i] = d.dx; sd.dy[i] = d.dy; sd.ln[i] = d.ln; sd.first[i] = total;
-		total += d.ln.nA + d.ln.nB;
+		total += (d.ln.nA + d.ln.nB + linesPerGroup - 1) / linesPerGroup;
 	}
 	sd.first[8] = total;
-	evB(e, 1);
-	if (total > 0) {
-		if (e->uniform && NK <= 2) {
-			const int align = e->maxNumDisp % 2 == 0 ? 2 : 1;
-#define SGM_LAUNCH_UNIFORM(NK_, AL_, DL_) hipLaunchKernelGGL((sgm_path_uniform_kernel<NK_, AL_, DL_, false>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->maxNumDisp, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
-			static const int stageMaxNK = [] { const char* v = getenv("SGMHIP_STAGE"); return v ? atoi(v) : 2; }();   // stage the delta bytes for up to this many entries per lane (0: never)
-			if (delta && e->maxNumDisp % 16 == 0 && NK <= stageMaxNK) {   // delta bytes staged through LDS, written out 16 bytes at a time
-#define SGM_LAUNCH_STAGED(NK_) hipLaunchKernelGGL((sgm_path_uniform_kernel<NK_, 2, true, true>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->maxNumDisp, e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, (int)P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
-				if (NK == 1) SGM_LAUNCH_STAGED(1); else SGM_LAUNCH_STAGED(2);
-#undef SGM_LAUNCH_STAGED
-			} else if (delta) {
-				if (NK == 1) { if (align == 2) SGM_LAUNCH_UNIFORM(1, 2, true); else SGM_LAUNCH_UNIFORM(1, 1, true); }
-				else { if (align == 2) SGM_LAUNCH_UNIFORM(2, 2, true); else SGM_LAUNCH_UNIFORM(2, 1, true); }
-			} else {
-				if (NK == 1) { if (align == 2) SGM_LAUNCH_UNIFORM(1, 2, false); else SGM_LAUNCH_UNIFORM(1, 1, false); }
-				else { if (align == 2) SGM_LAUNCH_UNIFORM(2, 2, false); else SGM_LAUNCH_UNIFORM(2, 1, false); }
-			}
-#undef SGM_LAUNCH_UNIFORM
+	return total;
+}
+
+extern "C++" {
+// the path kernel of the resident problem.  DL: L - C <= P2 as a byte per direction (a coalesced store per lane and step) instead of an atomic add into
+// the shared u16 sums
+template <bool DL>
+static void sgmLaunchPaths(sgmhip_engine* e, int P1, const SGMDirs& sd, int total) {
+	const int D = e->maxNumDisp, NK = D <= 64 ? 1 : (D <= 128 ? 2 : 4);
+#define SGM_PATH_TAIL e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, P1, sd, e->d_deltas, (unsigned long long)e->numCosts
+#define SGM_RAGGED(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, e->d_pixels, SGM_PATH_TAIL)
+#define SGM_UNIFORM(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, D, SGM_PATH_TAIL)
+#define SGM_SUB(LP_) do { if (D <= 64) SGM_RAGGED(sgm_path_sub_kernel<LP_, 64, DL>); else SGM_RAGGED(sgm_path_sub_kernel<LP_, 256, DL>); } while (0)
+	if (e->subGroups == 8) SGM_SUB(8);
+	else if (e->subGroups == 32) SGM_SUB(32);
+	else if (e->subGroups) SGM_SUB(16);
+	else if (e->uniform && NK <= 2) {   // the previous line of L in registers
+		if (DL && D % 16 == 0) {        // delta bytes staged through LDS, written out 16 bytes at a time
+			if (NK == 1) SGM_UNIFORM(sgm_path_uniform_kernel<1, 2, true, true>); else SGM_UNIFORM(sgm_path_uniform_kernel<2, 2, true, true>);
+		} else if (D % 2 == 0) {
+			if (NK == 1) SGM_UNIFORM(sgm_path_uniform_kernel<1, 2, DL, false>); else SGM_UNIFORM(sgm_path_uniform_kernel<2, 2, DL, false>);
+		} else {
+			if (NK == 1) SGM_UNIFORM(sgm_path_uniform_kernel<1, 1, DL, false>); else SGM_UNIFORM(sgm_path_uniform_kernel<2, 1, DL, false>);
 		}
-		else launchPath(e, e->stream, NK, total, (int)P1, sd, delta);
 	}
+	else if (NK == 1) SGM_RAGGED(sgm_path_kernel<1, DL>);
+	else if (NK == 2) SGM_RAGGED(sgm_path_kernel<2, DL>);
+	else SGM_RAGGED(sgm_path_kernel<4, DL>);
+#undef SGM_SUB
+#undef SGM_UNIFORM
+#undef SGM_RAGGED
+#undef SGM_PATH_TAIL
+}
+} // extern "C++"
+
+// cost volume, 8-path aggregation and winner-take-all of the resident problem (P2s already on the device: sgmSetP2s), asynchronous on the engine's stream.
+// Two mappings of work to lanes: one wavefront per line (subGroups == 0), or sub-groups of subGroups lanes per line and per pixel (sgm_kernels_sub.hip)
+static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
+	const int W = e->vw, H = e->vh, LP = e->subGroups;
+	const long nPix = (long)W * H;
+	// cost volume: one pixel per lane, 64-pixel tiles of a row per wave -- it serves the narrow ranges of the sub-group mapping too (0.9 against 1.28 ms of a
+	// sub-group per pixel pair for 3-12 disparities per pixel at 2048x1536).  One range for all pixels (wide mapping): the right-image strip of a tile sits in LDS
+	evB(e, 0);
+	{
+		const long nTiles = (long)((W + 63) / 64) * H;
+		const dim3 g((unsigned)((nTiles + 3) / 4));
+		if (e->uniform && !LP) {
+#define SGM_LAUNCH_UNI(MD_) hipLaunchKernelGGL((sgm_cost_uni_kernel<MD_>), g, dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->uniformMin, e->maxNumDisp, e->d_costs)
+			if (e->maxNumDisp <= 64) SGM_LAUNCH_UNI(64); else if (e->maxNumDisp <= 128) SGM_LAUNCH_UNI(128); else SGM_LAUNCH_UNI(256);
+#undef SGM_LAUNCH_UNI
+		} else hipLaunchKernelGGL(sgm_cost_px_kernel, g, dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->d_pixels, e->d_costs);
+	}
+	evE(e);
+	// DELTA aggregation: penalties that fit a byte (L - C <= P2), 8 scratch bytes per entry; no room for them: the atomic path
+	const bool delta = e->maxP2 <= 255 && ensureDeltas(e);
+	if (!delta) SGMCHK(e, hipMemsetAsync(e->d_accums, 0, (e->numCosts + 1) / 2 * 4, e->stream)); // imageAccumCosts.Memset(0), :990
+	SGMDirs sd;
+	const int total = sgmSchedule(W, H, LP ? 64 / LP : 1, sd);
+	evB(e, 1);
+	if (total > 0) { if (delta) sgmLaunchPaths<true>(e, (int)P1, sd, total); else sgmLaunchPaths<false>(e, (int)P1, sd, total); }
 	if (e->statsOn) e->stats.aggrLaunches += 1;
 	evE(e);
 	evB(e, 2);
 	if (delta) hipLaunchKernelGGL(sgm_sum_wta_kernel, dim3((unsigned)((nPix + 15) / 16)), dim3(256), 0, e->stream, e->d_pixels, e->d_costs, e->d_deltas, (unsigned long long)e->numCosts, e->d_accums, nPix, e->d_disp, e->d_cost);
 	else {
-		// winner-take-all: a wavefront per pixel spends most of its instructions on the 6-step reduction of 64 lanes; eight pixels per
-		// wavefront with a strided loop over the range need a fraction of the wave-instructions per pixel (same first minimum; SGMHIP_WTA_LANES =
-		// 64 selects the one-pixel kernel again)
-		static const int wtaLanes = [] { const char* v = getenv("SGMHIP_WTA_LANES"); const int n = v ? atoi(v) : 8; return (n == 8 || n == 16 || n == 32 || n == 64) ? n : 8; }();   // measured: 0.72 / 0.33 / 0.20 / 0.14 ms at 64 / 32 / 16 / 8 lanes (profiles/r02_sgm_wta_lanes.log)
-		if (wtaLanes == 8) hipLaunchKernelGGL((sgm_wta_sub_kernel<8>), dim3((unsigned)((nPix + 31) / 32)), dim3(256), 0, e->stream, e->d_pixels, e->d_accums, nPix, e->d_disp, e->d_cost);
-		else if (wtaLanes == 16) hipLaunchKernelGGL((sgm_wta_sub_kernel<16>), dim3((unsigned)((nPix + 15) / 16)), dim3(256), 0, e->stream, e->d_pixels, e->d_accums, nPix, e->d_disp, e->d_cost);
-		else if (wtaLanes == 32) hipLaunchKernelGGL((sgm_wta_sub_kernel<32>), dim3((unsigned)((nPix + 7) / 8)), dim3(256), 0, e->stream, e->d_pixels, e->d_accums, nPix, e->d_disp, e->d_cost);
-		else hipLaunchKernelGGL(sgm_wta_kernel, dim3((unsigned)((nPix + 3) / 4)), dim3(256), 0, e->stream, e->d_pixels, e->d_accums, nPix, e->d_disp, e->d_cost);
+		// winner-take-all over the atomic sums: a sub-group of lanes per pixel with a strided loop over its range.  The wide mapping takes 8 lanes: a wider group spends its
+		// instructions on the cross-lane reduction (measured: 0.72 / 0.33 / 0.20 / 0.14 ms at 64 / 32 / 16 / 8 lanes, profiles/r02_sgm_wta_lanes.log)
+		const int lanes = LP ? LP : 8;
+		const dim3 g((unsigned)((nPix + 4 * (64 / lanes) - 1) / (4 * (64 / lanes))));
+#define SGM_LAUNCH_WTA(LP_) hipLaunchKernelGGL((sgm_wta_sub_kernel<LP_>), g, dim3(256), 0, e->stream, e->d_pixels, e->d_accums, nPix, e->d_disp, e->d_cost)
+		if (lanes == 8) SGM_LAUNCH_WTA(8); else if (lanes == 32) SGM_LAUNCH_WTA(32); else SGM_LAUNCH_WTA(16);
+#undef SGM_LAUNCH_WTA
 	}
 	evE(e);
 	SGMCHK(e, hipGetLastError());
 	if (e->statsOn) e->stats.calls += 1;
+	return 0;
+}
+
+int sgmhip_match(sgmhip_engine* e, uint16_t P1, const uint16_t P2s[256], int sync) {
+	if (!e || !P2s || e->numCosts == 0) return SGMHIP_E_ARG;
+	SGMCHK(e, hipSetDevice(e->device));
+	{ const int rc = sgmSetP2s(e, P2s); if (rc) return rc; }
+	{ const int rc = sgmMatch(e, P1); if (rc) return rc; }
+	if (sync) SGMCHK(e, hipStreamSynchronize(e->stream));
 	return 0;
 }
 
@@ -338,6 +270,41 @@ int sgmhip_stats_get(sgmhip_engine* e, SGMHipStats* out) { if (!e || !out) retur
 namespace {
 using Scoped = DevBuf<unsigned char>;   // scoped device allocation (bytes) for the stateless helpers
 inline unsigned gridFor(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 65535); }
+
+// The steps that both a stateless call (upload, step, download) and a resident loop run: device pointers in, launches on `st`, nothing else.
+// FlipDirection: keys is scratch of w * h words
+hipError_t sgmFlip(hipStream_t st, const int16_t* l2r, int w, int h, uint32_t* keys, int16_t* r2l) {
+	const size_t n = (size_t)w * h;
+	const hipError_t r = hipMemsetAsync(keys, 0, n * 4, st);
+	if (r != hipSuccess) return r;
+	hipLaunchKernelGGL(sgmp_flip_scatter_kernel, dim3(gridFor(n)), dim3(256), 0, st, l2r, keys, w, h);
+	hipLaunchKernelGGL(sgmp_flip_decode_kernel, dim3(gridFor(n)), dim3(256), 0, st, (const uint32_t*)keys, r2l, n);
+	return hipSuccess;
+}
+// the speckle filter, in place: parent and size are scratch of w * h ints each
+void sgmSpeckles(hipStream_t st, int16_t* disp, int w, int h, int maxSpeckleSize, int maxDiff, int* parent, int* size) {
+	const int n = w * h; const unsigned g = gridFor((size_t)n);
+	hipLaunchKernelGGL(sgmp_speckle_init_kernel, dim3(g), dim3(256), 0, st, parent, size, n);
+	hipLaunchKernelGGL(sgmp_speckle_hook_kernel, dim3(g), dim3(256), 0, st, (const int16_t*)disp, parent, w, h, maxDiff);
+	hipLaunchKernelGGL(sgmp_speckle_flatten_kernel, dim3(g), dim3(256), 0, st, parent, size, n);
+	hipLaunchKernelGGL(sgmp_speckle_apply_kernel, dim3(g), dim3(256), 0, st, disp, (const int*)parent, (const int*)size, n, maxSpeckleSize);
+}
+// the device part of Disparity2RangeMap: the range of every pixel of a w x h disparity map
+void sgmRanges(hipStream_t st, const int16_t* disp, int w, int h, const uint8_t* mask2x, int w2, int minNumDisp, int minNumDispInvalid, short2* ranges) {
+	hipLaunchKernelGGL(sgmp_range_kernel, dim3(gridFor((size_t)w * h)), dim3(256), 0, st, disp, w, h, mask2x, w2, minNumDisp, minNumDispInvalid, ranges);
+}
+// ProjectDisparity2DepthMap of one pair (cost and conf may both be null): keys is scratch of dw * dh * 4 words, *numDepths (cleared by the caller) counts the depths
+hipError_t sgmProject(hipStream_t st, const int16_t* disp, const uint16_t* cost, int w, int h, const double Q[16], int subpixelSteps, unsigned long long* keys, int dw, int dh,
+		float* depth, float* range2, float* conf, unsigned* numDepths) {
+	const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
+	const hipError_t r = hipMemsetAsync(range2, 0, nd * 8, st);
+	if (r != hipSuccess) return r;
+	SGMPMat mq{}; memcpy(mq.m, Q, 128);
+	hipLaunchKernelGGL(sgmp_fill_u64, dim3(gridFor(nd * 4)), dim3(256), 0, st, keys, nd * 4, SGMP_KEY_NONE);
+	hipLaunchKernelGGL(sgmp_proj_splat_kernel, dim3(gridFor(n)), dim3(256), 0, st, disp, cost, w, h, mq, subpixelSteps, keys, dw, dh);
+	hipLaunchKernelGGL(sgmp_proj_resolve_kernel, dim3(gridFor(nd)), dim3(256), 0, st, disp, cost, w, mq, subpixelSteps, (const unsigned long long*)keys, dw, dh, depth, range2, conf, numDepths);
+	return hipSuccess;
+}
 }
 
 int sgmhip_consistency_cross_check(sgmhip_engine* e, int16_t* l2r, const int16_t* r2l, int wl, int h, int wr, int thCross) {
@@ -393,13 +360,11 @@ int sgmhip_upscale_mask(sgmhip_engine* e, const uint8_t* mask, int w, int h, uin
 int sgmhip_flip_direction(sgmhip_engine* e, const int16_t* l2r, int w, int h, int16_t* r2l) {
 	if (!e || !l2r || !r2l || w <= 0 || h <= 0 || w > 65534) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	Scoped a, k, b; const size_t n = (size_t)w * h;
-	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, k.alloc(n * 4)); SGMCHK(e, b.alloc(n * 2));
-	SGMCHK(e, hipMemcpyAsync(a.p, l2r, n * 2, hipMemcpyHostToDevice, e->stream));
-	SGMCHK(e, hipMemsetAsync(k.p, 0, n * 4, e->stream));
-	hipLaunchKernelGGL(sgmp_flip_scatter_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (const int16_t*)a.p, (uint32_t*)k.p, w, h);
-	hipLaunchKernelGGL(sgmp_flip_decode_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (const uint32_t*)k.p, (int16_t*)b.p, n);
-	SGMCHK(e, hipMemcpyAsync(r2l, b.p, n * 2, hipMemcpyDeviceToHost, e->stream));
+	DevBuf<int16_t> a, b; DevBuf<uint32_t> k; const size_t n = (size_t)w * h;
+	SGMCHK(e, a.alloc(n)); SGMCHK(e, k.alloc(n)); SGMCHK(e, b.alloc(n));
+	SGMCHK(e, hipMemcpyAsync(a, l2r, n * 2, hipMemcpyHostToDevice, e->stream));
+	SGMCHK(e, sgmFlip(e->stream, a, w, h, k, b));
+	SGMCHK(e, hipMemcpyAsync(r2l, b, n * 2, hipMemcpyDeviceToHost, e->stream));
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	return 0;
 }
@@ -419,12 +384,12 @@ int sgmhip_disparity2range_map(sgmhip_engine* e, const int16_t* disparity, int w
 		int minNumDisp, int minNumDispInvalid, SGMHipPixelData* pixels, uint64_t* numCosts, int* maxNumDisp) {
 	if (!e || !disparity || !mask2x || !pixels || w <= 0 || h <= 0 || w2 <= SGM_HW + 2 * w || h2 < SGM_HW + 2 * h) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	Scoped a, m, r; const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
-	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, m.alloc(n2)); SGMCHK(e, r.alloc(n * 4));
-	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream)); SGMCHK(e, hipMemcpyAsync(m.p, mask2x, n2, hipMemcpyHostToDevice, e->stream));
-	hipLaunchKernelGGL(sgmp_range_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (const int16_t*)a.p, w, h, (const uint8_t*)m.p, w2, minNumDisp, minNumDispInvalid, (short2*)r.p);
+	DevBuf<int16_t> a; DevBuf<uint8_t> m; DevBuf<short2> r; const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
+	SGMCHK(e, a.alloc(n)); SGMCHK(e, m.alloc(n2)); SGMCHK(e, r.alloc(n));
+	SGMCHK(e, hipMemcpyAsync(a, disparity, n * 2, hipMemcpyHostToDevice, e->stream)); SGMCHK(e, hipMemcpyAsync(m, mask2x, n2, hipMemcpyHostToDevice, e->stream));
+	sgmRanges(e->stream, a, w, h, m, w2, minNumDisp, minNumDispInvalid, r);
 	std::vector<int16_t> rg(n * 2);
-	SGMCHK(e, hipMemcpyAsync(rg.data(), r.p, n * 4, hipMemcpyDeviceToHost, e->stream));
+	SGMCHK(e, hipMemcpyAsync(rg.data(), r, n * 4, hipMemcpyDeviceToHost, e->stream));
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	// expansion to the 2x pixel table in raster order (:1409-1441): 2x pixel (R, C) takes the range of low-resolution pixel
 	// (R < HW+2 ? 0 : min((R-HW)/2, h-1), likewise for C); idx is the running sum of numDisp
@@ -480,22 +445,17 @@ int sgmhip_project_disparity2depth_map(sgmhip_engine* e, const int16_t* disparit
 		float* depthMap, float* depthRangeMap, float* confMap, int dw, int dh, int* anyDepth) {
 	if (!e || !disparity || !Q || !depthMap || !depthRangeMap || (cost && !confMap) || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || subpixelSteps <= 0 || (size_t)w * h > 0xFFFFFFFFull) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	Scoped a, c, k, d, rg, cf, cnt; const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
-	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, c.alloc(n * 2)); SGMCHK(e, k.alloc(nd * 4 * 8)); SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, rg.alloc(nd * 8)); SGMCHK(e, cf.alloc(nd * 4)); SGMCHK(e, cnt.alloc(4));
-	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
-	if (cost) SGMCHK(e, hipMemcpyAsync(c.p, cost, n * 2, hipMemcpyHostToDevice, e->stream));
-	SGMCHK(e, hipMemsetAsync(cnt.p, 0, 4, e->stream)); SGMCHK(e, hipMemsetAsync(rg.p, 0, nd * 8, e->stream));
-	SGMPMat mq{}; memcpy(mq.m, Q, 128);
-	const uint16_t* dc = cost ? (const uint16_t*)c.p : nullptr;
-	hipLaunchKernelGGL(sgmp_fill_u64, dim3(gridFor(nd * 4)), dim3(256), 0, e->stream, (unsigned long long*)k.p, nd * 4, SGMP_KEY_NONE);
-	hipLaunchKernelGGL(sgmp_proj_splat_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (const int16_t*)a.p, dc, w, h, mq, subpixelSteps, (unsigned long long*)k.p, dw, dh);
-	hipLaunchKernelGGL(sgmp_proj_resolve_kernel, dim3(gridFor(nd)), dim3(256), 0, e->stream, (const int16_t*)a.p, dc, w, mq, subpixelSteps, (const unsigned long long*)k.p, dw, dh,
-		(float*)d.p, (float*)rg.p, cost ? (float*)cf.p : nullptr, (unsigned*)cnt.p);
+	DevBuf<int16_t> a; DevBuf<uint16_t> c; DevBuf<unsigned long long> k; DevBuf<float> d, rg, cf; DevBuf<unsigned> cnt; const size_t n = (size_t)w * h, nd = (size_t)dw * dh;
+	SGMCHK(e, a.alloc(n)); SGMCHK(e, c.alloc(n)); SGMCHK(e, k.alloc(nd * 4)); SGMCHK(e, d.alloc(nd)); SGMCHK(e, rg.alloc(nd * 2)); SGMCHK(e, cf.alloc(nd)); SGMCHK(e, cnt.alloc(1));
+	SGMCHK(e, hipMemcpyAsync(a, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
+	if (cost) SGMCHK(e, hipMemcpyAsync(c, cost, n * 2, hipMemcpyHostToDevice, e->stream));
+	SGMCHK(e, hipMemsetAsync(cnt, 0, 4, e->stream));
+	SGMCHK(e, sgmProject(e->stream, a, cost ? c.p : nullptr, w, h, Q, subpixelSteps, k, dw, dh, d, rg, cost ? cf.p : nullptr, cnt));
 	unsigned num = 0;
-	SGMCHK(e, hipMemcpyAsync(depthMap, d.p, nd * 4, hipMemcpyDeviceToHost, e->stream));
-	SGMCHK(e, hipMemcpyAsync(depthRangeMap, rg.p, nd * 8, hipMemcpyDeviceToHost, e->stream));
-	if (cost) SGMCHK(e, hipMemcpyAsync(confMap, cf.p, nd * 4, hipMemcpyDeviceToHost, e->stream));
-	SGMCHK(e, hipMemcpyAsync(&num, cnt.p, 4, hipMemcpyDeviceToHost, e->stream));
+	SGMCHK(e, hipMemcpyAsync(depthMap, d, nd * 4, hipMemcpyDeviceToHost, e->stream));
+	SGMCHK(e, hipMemcpyAsync(depthRangeMap, rg, nd * 8, hipMemcpyDeviceToHost, e->stream));
+	if (cost) SGMCHK(e, hipMemcpyAsync(confMap, cf, nd * 4, hipMemcpyDeviceToHost, e->stream));
+	SGMCHK(e, hipMemcpyAsync(&num, cnt, 4, hipMemcpyDeviceToHost, e->stream));
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	if (anyDepth) *anyDepth = num > 0 ? 1 : 0;
 	return 0;
@@ -532,36 +492,31 @@ int sgmhip_fuse_disparities(sgmhip_engine* e, int nPairs, const int16_t* const* 
 	SGMCHK(e, hipSetDevice(e->device));
 	hipStream_t st = e->stream;
 	const size_t nd = (size_t)dw * dh;
-	std::vector<Scoped> maps((size_t)nPairs * 3);
-	Scoped k, cnt, d, c;
-	SGMCHK(e, k.alloc(nd * 4 * 8)); SGMCHK(e, cnt.alloc(4 * (size_t)std::max(nPairs, 1))); SGMCHK(e, d.alloc(nd * 4)); SGMCHK(e, c.alloc(nd * 4));
-	SGMCHK(e, hipMemsetAsync(cnt.p, 0, 4 * (size_t)std::max(nPairs, 1), st));
-	std::vector<Scoped> in((size_t)nPairs * 2);
+	std::vector<DevBuf<float>> maps((size_t)nPairs * 3);                     // depth, range (two floats per pixel) and confidence of every pair
+	DevBuf<unsigned long long> k; DevBuf<unsigned> cnt; DevBuf<float> d, c;
+	SGMCHK(e, k.alloc(nd * 4)); SGMCHK(e, cnt.alloc((size_t)std::max(nPairs, 1))); SGMCHK(e, d.alloc(nd)); SGMCHK(e, c.alloc(nd));
+	SGMCHK(e, hipMemsetAsync(cnt, 0, 4 * (size_t)std::max(nPairs, 1), st));
+	std::vector<DevBuf<int16_t>> disp((size_t)nPairs); std::vector<DevBuf<uint16_t>> cst((size_t)nPairs);
 	for (int p = 0; p < nPairs; ++p) {
 		const int w = widths[p], h = heights[p];
 		if (!disparities[p] || !costs[p] || w <= 0 || h <= 0 || subpixelSteps[p] <= 0 || (size_t)w * h > 0xFFFFFFFFull) return SGMHIP_E_ARG;
 		const size_t n = (size_t)w * h;
-		SGMCHK(e, in[p * 2].alloc(n * 2)); SGMCHK(e, in[p * 2 + 1].alloc(n * 2));
-		SGMCHK(e, maps[p * 3].alloc(nd * 4)); SGMCHK(e, maps[p * 3 + 1].alloc(nd * 8)); SGMCHK(e, maps[p * 3 + 2].alloc(nd * 4));
-		SGMCHK(e, hipMemcpyAsync(in[p * 2].p, disparities[p], n * 2, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(in[p * 2 + 1].p, costs[p], n * 2, hipMemcpyHostToDevice, st));
-		SGMCHK(e, hipMemsetAsync(maps[p * 3 + 1].p, 0, nd * 8, st));
-		SGMPMat mq{}; memcpy(mq.m, Qs + 16 * p, 128);
-		hipLaunchKernelGGL(sgmp_fill_u64, dim3(gridFor(nd * 4)), dim3(256), 0, st, (unsigned long long*)k.p, nd * 4, SGMP_KEY_NONE);
-		hipLaunchKernelGGL(sgmp_proj_splat_kernel, dim3(gridFor(n)), dim3(256), 0, st, (const int16_t*)in[p * 2].p, (const uint16_t*)in[p * 2 + 1].p, w, h, mq, subpixelSteps[p], (unsigned long long*)k.p, dw, dh);
-		hipLaunchKernelGGL(sgmp_proj_resolve_kernel, dim3(gridFor(nd)), dim3(256), 0, st, (const int16_t*)in[p * 2].p, (const uint16_t*)in[p * 2 + 1].p, w, mq, subpixelSteps[p],
-			(const unsigned long long*)k.p, dw, dh, (float*)maps[p * 3].p, (float*)maps[p * 3 + 1].p, (float*)maps[p * 3 + 2].p, (unsigned*)cnt.p + p);
+		SGMCHK(e, disp[p].alloc(n)); SGMCHK(e, cst[p].alloc(n));
+		SGMCHK(e, maps[p * 3].alloc(nd)); SGMCHK(e, maps[p * 3 + 1].alloc(nd * 2)); SGMCHK(e, maps[p * 3 + 2].alloc(nd));
+		SGMCHK(e, hipMemcpyAsync(disp[p], disparities[p], n * 2, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(cst[p], costs[p], n * 2, hipMemcpyHostToDevice, st));
+		SGMCHK(e, sgmProject(st, disp[p], cst[p], w, h, Qs + 16 * p, subpixelSteps[p], k, dw, dh, maps[p * 3], maps[p * 3 + 1], maps[p * 3 + 2], cnt.p + p));
 	}
 	std::vector<unsigned> num((size_t)std::max(nPairs, 1), 0u);
-	if (nPairs) SGMCHK(e, hipMemcpyAsync(num.data(), cnt.p, 4 * (size_t)nPairs, hipMemcpyDeviceToHost, st));
+	if (nPairs) SGMCHK(e, hipMemcpyAsync(num.data(), cnt, 4 * (size_t)nPairs, hipMemcpyDeviceToHost, st));
 	SGMCHK(e, hipStreamSynchronize(st));
 	SGMPPairs pr{}; int used = 0;
-	for (int p = 0; p < nPairs; ++p) if (num[p] > 0) { pr.depth[used] = (const float*)maps[p * 3].p; pr.range[used] = (const float*)maps[p * 3 + 1].p; pr.conf[used] = (const float*)maps[p * 3 + 2].p; ++used; }
+	for (int p = 0; p < nPairs; ++p) if (num[p] > 0) { pr.depth[used] = maps[p * 3]; pr.range[used] = maps[p * 3 + 1]; pr.conf[used] = maps[p * 3 + 2]; ++used; }
 	if (nUsed) *nUsed = used;
 	if (used == 0) { memset(depthMap, 0, nd * 4); memset(confMap, 0, nd * 4); return 0; }
-	hipLaunchKernelGGL(sgmp_fuse_pairs_kernel, dim3(gridFor(nd)), dim3(256), 0, st, pr, used, nd, minViews, (float*)d.p, (float*)c.p);
+	hipLaunchKernelGGL(sgmp_fuse_pairs_kernel, dim3(gridFor(nd)), dim3(256), 0, st, pr, used, nd, minViews, d, c);
 	SGMCHK(e, hipGetLastError());
-	SGMCHK(e, hipMemcpyAsync(depthMap, d.p, nd * 4, hipMemcpyDeviceToHost, st));
-	SGMCHK(e, hipMemcpyAsync(confMap, c.p, nd * 4, hipMemcpyDeviceToHost, st));
+	SGMCHK(e, hipMemcpyAsync(depthMap, d, nd * 4, hipMemcpyDeviceToHost, st));
+	SGMCHK(e, hipMemcpyAsync(confMap, c, nd * 4, hipMemcpyDeviceToHost, st));
 	SGMCHK(e, hipStreamSynchronize(st));
 	return 0;
 }
@@ -569,15 +524,11 @@ int sgmhip_fuse_disparities(sgmhip_engine* e, int nPairs, const int16_t* const* 
 int sgmhip_filter_speckles(sgmhip_engine* e, int16_t* disparity, int w, int h, int maxSpeckleSize, int maxDiff) {
 	if (!e || !disparity || w <= 0 || h <= 0 || maxSpeckleSize < 0 || maxDiff < 0 || (size_t)w * h > 0x7fffffffull) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	Scoped a, p, z; const size_t n = (size_t)w * h;
-	SGMCHK(e, a.alloc(n * 2)); SGMCHK(e, p.alloc(n * 4)); SGMCHK(e, z.alloc(n * 4));
-	SGMCHK(e, hipMemcpyAsync(a.p, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
-	const unsigned g = gridFor(n);
-	hipLaunchKernelGGL(sgmp_speckle_init_kernel, dim3(g), dim3(256), 0, e->stream, (int*)p.p, (int*)z.p, (int)n);
-	hipLaunchKernelGGL(sgmp_speckle_hook_kernel, dim3(g), dim3(256), 0, e->stream, (const int16_t*)a.p, (int*)p.p, w, h, maxDiff);
-	hipLaunchKernelGGL(sgmp_speckle_flatten_kernel, dim3(g), dim3(256), 0, e->stream, (int*)p.p, (int*)z.p, (int)n);
-	hipLaunchKernelGGL(sgmp_speckle_apply_kernel, dim3(g), dim3(256), 0, e->stream, (int16_t*)a.p, (const int*)p.p, (const int*)z.p, (int)n, maxSpeckleSize);
-	SGMCHK(e, hipMemcpyAsync(disparity, a.p, n * 2, hipMemcpyDeviceToHost, e->stream));
+	DevBuf<int16_t> a; DevBuf<int> p, z; const size_t n = (size_t)w * h;
+	SGMCHK(e, a.alloc(n)); SGMCHK(e, p.alloc(n)); SGMCHK(e, z.alloc(n));
+	SGMCHK(e, hipMemcpyAsync(a, disparity, n * 2, hipMemcpyHostToDevice, e->stream));
+	sgmSpeckles(e->stream, a, w, h, maxSpeckleSize, maxDiff, p, z);
+	SGMCHK(e, hipMemcpyAsync(disparity, a, n * 2, hipMemcpyDeviceToHost, e->stream));
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	return 0;
 }
@@ -619,32 +570,32 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 	hipStream_t st = e->stream;
 	const size_t nFull = (size_t)w * h, nValid = (size_t)(w - 2 * SGM_HW) * (h - 2 * SGM_HW);
 	// the per-level working set (sized for the finest level)
-	Scoped lB, rB, lG, rG, lM, rM, lM2, rM2, lD, rD, lDn, rDn, keys, ranges, tiles, scal, par, siz;
-	SGMCHK(e, lB.alloc(nFull * 3)); SGMCHK(e, rB.alloc(nFull * 3)); SGMCHK(e, lG.alloc(nFull * 4)); SGMCHK(e, rG.alloc(nFull * 4));
+	DevBuf<unsigned char> lB, rB; DevBuf<float> lG, rG; DevBuf<uint8_t> lM, rM, lM2, rM2; DevBuf<int16_t> lD, rD, lDn, rDn;
+	DevBuf<uint32_t> keys; DevBuf<short2> ranges; DevBuf<unsigned long long> tiles, scal; DevBuf<int> par, siz;
+	SGMCHK(e, lB.alloc(nFull * 3)); SGMCHK(e, rB.alloc(nFull * 3)); SGMCHK(e, lG.alloc(nFull)); SGMCHK(e, rG.alloc(nFull));
 	SGMCHK(e, lM.alloc(nValid)); SGMCHK(e, rM.alloc(nValid)); SGMCHK(e, lM2.alloc(nValid)); SGMCHK(e, rM2.alloc(nValid));
-	SGMCHK(e, lD.alloc(nValid * 2)); SGMCHK(e, rD.alloc(nValid * 2)); SGMCHK(e, lDn.alloc(nValid * 2)); SGMCHK(e, rDn.alloc(nValid * 2));
-	SGMCHK(e, keys.alloc(nValid * 4)); SGMCHK(e, ranges.alloc(nValid * 4)); SGMCHK(e, par.alloc(nValid * 4)); SGMCHK(e, siz.alloc(nValid * 4));
+	SGMCHK(e, lD.alloc(nValid)); SGMCHK(e, rD.alloc(nValid)); SGMCHK(e, lDn.alloc(nValid)); SGMCHK(e, rDn.alloc(nValid));
+	SGMCHK(e, keys.alloc(nValid)); SGMCHK(e, ranges.alloc(nValid)); SGMCHK(e, par.alloc(nValid)); SGMCHK(e, siz.alloc(nValid));
 	const int maxTiles = (int)((nValid + SGMT_TILE - 1) / SGMT_TILE);
-	SGMCHK(e, tiles.alloc((size_t)maxTiles * 8)); SGMCHK(e, scal.alloc(16));
-	SGMCHK(e, hipMemcpyAsync(e->d_P2s, P2s, 512, hipMemcpyHostToDevice, st));
-	e->maxP2 = 0; for (int i = 0; i < 256; ++i) e->maxP2 = std::max(e->maxP2, (int)P2s[i]);
+	SGMCHK(e, tiles.alloc((size_t)maxTiles)); SGMCHK(e, scal.alloc(2));     // scal: {numCosts, maxNumDisp} of a level's range table
+	{ const int rc = sgmSetP2s(e, P2s); if (rc) return rc; }
 
-	int16_t* leftDisp = (int16_t*)lD.p; int16_t* rightDisp = (int16_t*)rD.p; int16_t* leftNew = (int16_t*)lDn.p; int16_t* rightNew = (int16_t*)rDn.p;
-	uint8_t* lm = (uint8_t*)lM.p; uint8_t* rm = (uint8_t*)rM.p; uint8_t* lmNext = (uint8_t*)lM2.p; uint8_t* rmNext = (uint8_t*)rM2.p;
+	int16_t *leftDisp = lD, *rightDisp = rD, *leftNew = lDn, *rightNew = rDn;
+	uint8_t *lm = lM, *rm = rM, *lmNext = lM2, *rmNext = rM2;
 	int dW = 0, dH = 0;            // size of leftDisp (the previous level's valid grid)
 	int mW = 0, mH = 0;            // size of the masks
 	int levels = 0;
 	bool first = true;
 	// Disparity2RangeMap on the device + Match of (bgr, grayA -> grayB) with those ranges; the result is copied to `out`
-	auto rangeAndMatch = [&](const int16_t* disp, const uint8_t* mask2x, int vw, int vh, int lw, int lh, const void* bgr, const void* gA, const void* gB, int a, int b, int16_t* out) -> int {
-		const size_t n = (size_t)dW * dH, n2 = (size_t)vw * vh;
-		hipLaunchKernelGGL(sgmp_range_kernel, dim3(gridFor(n)), dim3(256), 0, st, disp, dW, dH, mask2x, vw, a, b, (short2*)ranges.p);
+	auto rangeAndMatch = [&](const int16_t* disp, const uint8_t* mask2x, int vw, int vh, int lw, int lh, const unsigned char* bgr, const float* gA, const float* gB, int a, int b, int16_t* out) -> int {
+		const size_t n2 = (size_t)vw * vh;
+		sgmRanges(st, disp, dW, dH, mask2x, vw, a, b, ranges);
 		const int nT = (int)((n2 + SGMT_TILE - 1) / SGMT_TILE);
-		SGMCHK(e, hipMemsetAsync(scal.p, 0, 16, st));
-		hipLaunchKernelGGL(sgmt_tile_sums_kernel, dim3(nT), dim3(256), 0, st, (const short2*)ranges.p, dW, dH, vw, n2, (unsigned long long*)tiles.p, (int*)((char*)scal.p + 8));
-		hipLaunchKernelGGL(sgmt_scan_tiles_kernel, dim3(1), dim3(256), 0, st, (unsigned long long*)tiles.p, nT, (unsigned long long*)scal.p);
+		SGMCHK(e, hipMemsetAsync(scal, 0, 16, st));
+		hipLaunchKernelGGL(sgmt_tile_sums_kernel, dim3(nT), dim3(256), 0, st, (const short2*)ranges.p, dW, dH, vw, n2, tiles.p, (int*)(scal.p + 1));
+		hipLaunchKernelGGL(sgmt_scan_tiles_kernel, dim3(1), dim3(256), 0, st, tiles.p, nT, scal.p);
 		unsigned long long hs[2] = {0, 0};
-		SGMCHK(e, hipMemcpyAsync(hs, scal.p, 16, hipMemcpyDeviceToHost, st));
+		SGMCHK(e, hipMemcpyAsync(hs, scal, 16, hipMemcpyDeviceToHost, st));
 		SGMCHK(e, hipStreamSynchronize(st));
 		const uint64_t numCosts = hs[0]; const int mx = (int)(hs[1] & 0xffffffffull);
 		if (numCosts == 0 || mx <= 0 || mx > 256) { e->err = "tsgm: empty or too wide disparity ranges at a level"; return SGMHIP_E_ARG; }
@@ -663,24 +614,16 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 		SGMCHK(e, hipMemcpyAsync(out, e->d_disp, n2 * 2, hipMemcpyDeviceToDevice, st));
 		return 0;
 	};
-	auto speckles = [&](int16_t* d, int vw, int vh) {
-		const int n = vw * vh; const unsigned g = gridFor((size_t)n);
-		hipLaunchKernelGGL(sgmp_speckle_init_kernel, dim3(g), dim3(256), 0, st, (int*)par.p, (int*)siz.p, n);
-		hipLaunchKernelGGL(sgmp_speckle_hook_kernel, dim3(g), dim3(256), 0, st, (const int16_t*)d, (int*)par.p, vw, vh, 5);
-		hipLaunchKernelGGL(sgmp_speckle_flatten_kernel, dim3(g), dim3(256), 0, st, (int*)par.p, (int*)siz.p, n);
-		hipLaunchKernelGGL(sgmp_speckle_apply_kernel, dim3(g), dim3(256), 0, st, d, (const int*)par.p, (const int*)siz.p, n, nSpeckleSize);
-	};
 	for (int lvl = k; lvl >= 0; --lvl) {
 		const int f = 1 << lvl, lw = w / f, lh = h / f, vw = lw - 2 * SGM_HW, vh = lh - 2 * SGM_HW;
 		const size_t nImg = (size_t)lw * lh, nV = (size_t)vw * vh;
-		const void *pLB, *pRB, *pLG, *pRG;
-		if (f == 1) { pLB = fLB; pRB = fRB; pLG = fLG; pRG = fRG; }
-		else {
-			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, fLB, w, (unsigned char*)lB.p, lw, lh, f);
-			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, fRB, w, (unsigned char*)rB.p, lw, lh, f);
-			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, fLG, w, (float*)lG.p, lw, lh, f);
-			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, fRG, w, (float*)rG.p, lw, lh, f);
-			pLB = lB.p; pRB = rB.p; pLG = lG.p; pRG = rG.p;
+		const unsigned char *pLB = fLB, *pRB = fRB; const float *pLG = fLG, *pRG = fRG;
+		if (f != 1) {
+			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, fLB, w, lB.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_u8x3_kernel, dim3(gridFor(nImg * 3)), dim3(256), 0, st, fRB, w, rB.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, fLG, w, lG.p, lw, lh, f);
+			hipLaunchKernelGGL(sgmt_area_f32_kernel, dim3(gridFor(nImg)), dim3(256), 0, st, fRG, w, rG.p, lw, lh, f);
+			pLB = lB; pRB = rB; pLG = lG; pRG = rG;
 		}
 		if (first) {
 			const int hw2 = cvRound(lw * 0.5), hh2 = cvRound(lh * 0.5);                 // Image8U::computeResize(size, 0.5), :622
@@ -698,10 +641,7 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 		mW = vw; mH = vh;
 		const int a = first ? 11 : 5, b = first ? 33 : 7;
 		// right -> left with ranges from the flipped previous disparities (:641-654)
-		const size_t nD = (size_t)dW * dH;
-		SGMCHK(e, hipMemsetAsync(keys.p, 0, nD * 4, st));
-		hipLaunchKernelGGL(sgmp_flip_scatter_kernel, dim3(gridFor(nD)), dim3(256), 0, st, (const int16_t*)leftDisp, (uint32_t*)keys.p, dW, dH);
-		hipLaunchKernelGGL(sgmp_flip_decode_kernel, dim3(gridFor(nD)), dim3(256), 0, st, (const uint32_t*)keys.p, rightDisp, nD);
+		SGMCHK(e, sgmFlip(st, leftDisp, dW, dH, keys, rightDisp));
 		{ const int rc = rangeAndMatch(rightDisp, rm, vw, vh, lw, lh, pRB, pRG, pLG, a, b, rightNew); if (rc) return rc; }
 		// left -> right (:657-667)
 		{ const int rc = rangeAndMatch(leftDisp, lm, vw, vh, lw, lh, pLB, pLG, pRG, a, b, leftNew); if (rc) return rc; }
@@ -710,7 +650,7 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 		hipLaunchKernelGGL(sgmp_cross_check_kernel, dim3(gridFor(nV)), dim3(256), 0, st, leftDisp, (const int16_t*)rightDisp, vw, vw, vh, 1);
 		if (first) {                                                                   // :680-690
 			hipLaunchKernelGGL(sgmp_cross_check_kernel, dim3(gridFor(nV)), dim3(256), 0, st, rightDisp, (const int16_t*)leftDisp, vw, vw, vh, 1);
-			speckles(leftDisp, vw, vh); speckles(rightDisp, vw, vh);
+			sgmSpeckles(st, leftDisp, vw, vh, nSpeckleSize, 5, par, siz); sgmSpeckles(st, rightDisp, vw, vh, nSpeckleSize, 5, par, siz);
 			hipLaunchKernelGGL(sgmp_extract_mask_kernel, dim3((vh + 63) / 64), dim3(64), 0, st, (const int16_t*)leftDisp, lm, vw, vh, 3);
 			hipLaunchKernelGGL(sgmp_extract_mask_kernel, dim3((vh + 63) / 64), dim3(64), 0, st, (const int16_t*)rightDisp, rm, vw, vh, 3);
 		}

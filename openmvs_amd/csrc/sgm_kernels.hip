@@ -2,10 +2,11 @@
 // (libs/MVS/SemiGlobalMatcher.cpp:863-1302): WZNCC cost volume, 8-path aggregation, winner-take-all.
 //
 // Layout is the reference's: a ragged cost volume, pixel p owns numDisp(p) consecutive entries at
-// PixelData::idx (u8 costs, u16 path sums).  All three kernels map the 64 lanes of a wave onto the
+// PixelData::idx (u8 costs, u16 path sums).  The path kernels map the 64 lanes of a wave onto the
 // disparities of ONE pixel, so a wave's accesses to costs / sums are one contiguous 64..128-byte
 // segment (coalesced), the cross-disparity minimum is a wave reduction, and the path recurrence
-// L(d) <- Lp(d-1), Lp(d), Lp(d+1) goes through a 2-slot LDS line buffer.  Integer work is exact.
+// L(d) <- Lp(d-1), Lp(d), Lp(d+1) goes through a 2-slot LDS line buffer; the cost kernels give a
+// lane a pixel, and the winner-take-all is sgm_wta_sub_kernel (sgm_kernels_sub.hip).  Integer work is exact.
 //
 // The aggregation is a chain of dependent pixels along each path, so one wave owns one line and
 // walks it in chunks of SGM_T pixels: the PixelData, cost bytes and running sums of a whole chunk
@@ -35,15 +36,10 @@ typedef const unsigned short* sgm_gcs;
 __device__ __forceinline__ int sgm_round2int(float x) { return (int)pm_floorf(x + .5f); } // ROUND2INT, Types.h:949-955
 
 // ---- cost volume, SemiGlobalMatcher.cpp:874-985 --------------------------------------------------------------------------
-// The kernel is fp32-VALU bound (49 taps x 3 running sums per cost, all in the reference's summation order), so the design goal
-// is wave-instructions per cost:
-//  * the per-pixel prologue (weighted mean and variance of the left window, :905-935) is two serial 49-term sums; done by the
-//    wave that owns the pixel it costs 196 wave-instructions per pixel, done one pixel per LANE (sgm_setup_kernel) it costs 1/64
-//    of that.  Its three results per pixel travel through a 16-byte record;
-//  * a wave computes the costs of TWO horizontally adjacent pixels, one disparity of each per lane, as float2 lanes: the three
-//    multiply-add pairs of a tap become v_pk_mul_f32 / v_pk_add_f32 (IEEE, unfused: -ffp-contract=off), and one ds_read_b128
-//    delivers the weights of both pixels.
-typedef float sgm_v2f __attribute__((ext_vector_type(2)));
+// The kernels are fp32-VALU bound (49 taps x 3 running sums per cost, all in the reference's summation order), so the design goal
+// is wave-instructions per cost.  The per-pixel prologue (weighted mean and variance of the left window, :905-935) is two serial
+// 49-term sums: done by a wave that owns the pixel it costs 196 wave-instructions per pixel, done one pixel per LANE it costs 1/64
+// of that -- so a lane owns a pixel in both kernels below, prologue and costs alike.
 #if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
 #define SGM_SCHED_BARRIER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)   // no memory access is moved and nothing is scheduled across this point
 #define SGM_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
@@ -65,30 +61,6 @@ __device__ __forceinline__ float sgm_weight(const unsigned char* __restrict__ co
 	return pm_expf(wColor + wSpatial);
 }
 
-// one valid-grid pixel per lane: {sumW, mean, normSq0, 0}
-__global__ __launch_bounds__(256) void sgm_setup_kernel(const unsigned char* __restrict__ colorL, const float* __restrict__ grayL,
-		int w, int vw, int vh, const SGMPixel* __restrict__ pixels, float4* __restrict__ setup) {
-	const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
-	if (pix >= (long)vw * vh) return;
-	const SGMPixel px = pixels[pix];
-	if (!(px.minDisp < px.maxDisp)) { setup[pix] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-	const int ux = (int)(pix % vw) + SGM_HW, uy = (int)(pix / vw) + SGM_HW;
-	float wk[SGM_NT], vk[SGM_NT];
-	float acc = 0.f, sumW = 0.f;
-#pragma unroll
-	for (int k = 0; k < SGM_NT; ++k) {
-		const int i = k / 7 - SGM_HW, j = k % 7 - SGM_HW;
-		wk[k] = sgm_weight(colorL, w, ux, uy, i, j);
-		vk[k] = grayL[(size_t)(uy + i) * w + (ux + j)];
-		acc += vk[k] * wk[k]; sumW += wk[k];
-	}
-	const float tm = acc / sumW;
-	float normSq0 = 0.f;
-#pragma unroll
-	for (int k = 0; k < SGM_NT; ++k) { const float t = vk[k] - tm; const float tw = wk[k] * t; normSq0 += tw * t; }
-	setup[pix] = make_float4(sumW, tm, normSq0, 0.f);
-}
-
 __device__ __forceinline__ unsigned char sgm_cost_of(float sum, float sumSq, float nom, float sumW, float normSq0) {
 	const float eps = 1e-3f;
 	const float normSq1 = sumSq - (sum * sum) / sumW;
@@ -96,81 +68,15 @@ __device__ __forceinline__ unsigned char sgm_cost_of(float sum, float sumSq, flo
 	return ncc <= 0 ? (unsigned char)255 : (unsigned char)sgm_round2int((1.f - pm_minf(ncc, 1.f)) * 255.f);
 }
 
-// one wave per pair of horizontally adjacent valid-grid pixels (A, B = A + 1)
-__global__ __launch_bounds__(256, 4) void sgm_cost_kernel(const unsigned char* __restrict__ colorL, const float* __restrict__ grayL,
-		const float* __restrict__ grayR, int w, int h, int vw, int vh, const SGMPixel* __restrict__ pixels,
-		const float4* __restrict__ setup, unsigned char* __restrict__ costs) {
-	__shared__ float4 s_w[4][SGM_NT + 1];                              // (wA, wB, wA*(vA-meanA), wB*(vB-meanB)) per tap
-	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const int ppr = (vw + 1) >> 1;                                     // pairs per row
-	const long pair = (long)blockIdx.x * 4 + wave;
-	if (pair >= (long)ppr * vh) return;                                // (no workgroup barrier below: each wave owns its LDS rows)
-	const int row = (int)(pair / ppr), colA = (int)(pair % ppr) * 2;
-	const long pixA = (long)row * vw + colA;
-	const bool hasB = colA + 1 < vw;
-	const SGMPixel pxA = pixels[pixA];
-	SGMPixel pxB; pxB.idx = 0; pxB.minDisp = 0; pxB.maxDisp = 0; pxB.pad = 0;
-	if (hasB) pxB = pixels[pixA + 1];
-	const int nDA = pxA.maxDisp > pxA.minDisp ? pxA.maxDisp - pxA.minDisp : 0;
-	const int nDB = pxB.maxDisp > pxB.minDisp ? pxB.maxDisp - pxB.minDisp : 0;
-	if (nDA == 0 && nDB == 0) return;
-	const int ux = colA + SGM_HW, uy = row + SGM_HW;                   // pixel A in image coordinates; B is at ux + 1
-	const float4 sA = setup[pixA];
-	const float4 sB = hasB ? setup[pixA + 1] : make_float4(1.f, 0.f, 0.f, 0.f);
-	if (lane < SGM_NT) {
-		const int i = lane / 7 - SGM_HW, j = lane % 7 - SGM_HW;
-		float wA = 0.f, wB = 0.f, tA = 0.f, tB = 0.f;
-		if (nDA) { wA = sgm_weight(colorL, w, ux, uy, i, j); tA = wA * (grayL[(size_t)(uy + i) * w + (ux + j)] - sA.y); }
-		if (nDB) { wB = sgm_weight(colorL, w, ux + 1, uy, i, j); tB = wB * (grayL[(size_t)(uy + i) * w + (ux + 1 + j)] - sB.y); }
-		s_w[wave][lane] = make_float4(wA, wB, tA, tB);
-	}
-	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	const int nDmax = nDA > nDB ? nDA : nDB;
-#pragma unroll 1
-	for (int k = lane; k < nDmax; k += 64) {
-		asm volatile("" ::: "memory");   // keep the 49 weight reads inside the iteration (hoisted, they occupy 196 VGPRs and spill)
-		const int dA = pxA.minDisp + k, dB = pxB.minDisp + k;
-		const bool actA = k < nDA, actB = k < nDB;
-		const bool inA = actA && !(ux - SGM_HW + dA < 0 || ux + SGM_HW + dA >= w);       // all taps inside the right image (:954-957)
-		const bool inB = actB && !(ux + 1 - SGM_HW + dB < 0 || ux + 1 + SGM_HW + dB >= w);
-		const int cA = inA ? ux + dA : SGM_HW, cB = inB ? ux + 1 + dB : SGM_HW;           // a safe column for lanes that will not use the result
-		sgm_v2f sum = {0.f, 0.f}, sumSq = {0.f, 0.f}, nom = {0.f, 0.f};
-		int n = 0;
-		for (int i = -SGM_HW; i <= SGM_HW; ++i) {
-			const float* rowA = grayR + (size_t)(uy + i) * w + cA;
-			const float* rowB = grayR + (size_t)(uy + i) * w + cB;
-#pragma unroll
-			for (int j = -SGM_HW; j <= SGM_HW; ++j) {
-#ifdef SGM_PROBE_NO_LOADS      /* timing probes (never in the product build; results are not the reference's): what bounds the cost kernel? */
-				const sgm_v2f f = {0.3f + 0.001f * (float)(j + k), 0.4f + 0.001f * (float)(i + k)};
-#else
-				const sgm_v2f f = {rowA[j], rowB[j]};
-#endif
-#ifdef SGM_PROBE_NO_WEIGHT_READS
-				const float4 pw = make_float4(0.02f, 0.021f, 0.003f * (float)n, 0.002f * (float)n); ++n;
-#else
-				const float4 pw = s_w[wave][n++];
-#endif
-				const sgm_v2f pww = {pw.x, pw.y}, pwt = {pw.z, pw.w};
-				const sgm_v2f fw = f * pww;
-				sum += fw; sumSq += f * fw; nom += f * pwt;
-			}
-		}
-		if (actA) costs[pxA.idx + (unsigned)k] = inA ? sgm_cost_of(sum.x, sumSq.x, nom.x, sA.x, sA.z) : (unsigned char)255;
-		if (actB) costs[pxB.idx + (unsigned)k] = inB ? sgm_cost_of(sum.y, sumSq.y, nom.y, sB.x, sB.z) : (unsigned char)255;
-	}
-}
-
-// ---- the same cost volume with one valid-grid pixel per LANE ---------------------------------------------------------------------------------------
-// sgm_cost_kernel spends, per 64 costs, 49 broadcast ds_read_b128 (the pixel's weights are wave-uniform there), 28 unaligned multi-dword loads
-// and 294 packed VALU instructions, and the three units overlap badly (probes: r02_sgm_cost_probes.log; packed fp32 multiplies and adds move no more
-// flops per cycle than plain ones on this part: r03_valu_rate.log).  Here a lane owns a pixel and walks its disparities: the 49 weights w and the
-// 49 products w*(v-mean) live in the lane's registers for the whole walk (or the products in a lane-private LDS column, SGM_PX_T_IN_LDS),
-// the 7x7 window of the right image slides with the disparity (7 new texels per cost; the loads of neighbouring lanes are neighbouring addresses),
-// and what remains per cost is the arithmetic the reference's summation order demands: 49 x (2 mul + 1 add, 1 mul + 1 add, 1 mul + 1 add), all
-// full-rate VOP2.  The prologue of sgm_setup_kernel (weighted mean / variance of the left window) is the same 49 weights and is done here too --
-// no setup pass, no 16-byte record.  A lane collects four costs in a register and stores them as one aligned dword of its pixel's run.
+// ---- one valid-grid pixel per LANE ----------------------------------------------------------------------------------------------------------------
+// A wave that computes the costs of one pixel (or a pair), a disparity per lane, spends per 64 costs 49 broadcast ds_read_b128 (the pixel's weights are
+// wave-uniform there), 28 unaligned multi-dword loads and 294 packed VALU instructions, and the three units overlap badly (probes: r02_sgm_cost_probes.log;
+// packed fp32 multiplies and adds move no more flops per cycle than plain ones on this part: r03_valu_rate.log).  Here a lane owns a pixel and walks its
+// disparities: the 49 weights w and the 49 products w*(v-mean) live in the lane's registers for the whole walk (or the products in a lane-private LDS
+// column, SGM_PX_T_IN_LDS), the 7x7 window of the right image slides with the disparity (7 new texels per cost; the loads of neighbouring lanes are
+// neighbouring addresses), and what remains per cost is the arithmetic the reference's summation order demands: 49 x (2 mul + 1 add, 1 mul + 1 add,
+// 1 mul + 1 add), all full-rate VOP2.  The left-window prologue uses the same 49 weights and is done here too -- no setup pass, no per-pixel record in
+// memory.  A lane collects four costs in a register and stores them as one aligned dword of its pixel's run.
 #ifndef SGM_PX_T_IN_LDS
 #define SGM_PX_T_IN_LDS 0   // 1: the 49 products w*(v-mean) in a lane-private LDS column (167 VGPRs, 3 waves per SIMD) instead of registers (221 VGPRs, 2 waves).
 #endif                      // Measured at 2048x1536 (profiles/r03_sgm_call12.log, r03_sgm_call11_px_cost_u64.log): D = 64: 2.24 vs 2.22 ms, D = 128: 4.32 vs 3.71 ms -- the
@@ -871,21 +777,4 @@ __global__ __launch_bounds__(256) void sgm_sum_wta_kernel(const SGMPixel* __rest
 		if (nD <= 0) { disp[pix] = px.minDisp; cost[pix] = 0xFFFF; }
 		else { disp[pix] = (short)(px.minDisp + (int)(key & 0xFFFFu)); cost[pix] = (unsigned short)(key >> 16); }
 	}
-}
-
-// ---- winner-take-all, SemiGlobalMatcher.cpp:1272-1301: one wave per pixel --------------------
-__global__ __launch_bounds__(256) void sgm_wta_kernel(const SGMPixel* __restrict__ pixels, const unsigned short* __restrict__ accums,
-		long nPix, short* __restrict__ disp, unsigned short* __restrict__ cost) {
-	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const long pix = (long)blockIdx.x * 4 + wave;
-	if (pix >= nPix) return;
-	const SGMPixel px = pixels[pix];
-	const int nD = px.maxDisp - px.minDisp;
-	if (nD <= 0) { if (lane == 0) { disp[pix] = px.minDisp; cost[pix] = 0xFFFF; } return; }
-	// first minimum == lexicographic minimum of (value, index)
-	unsigned key = 0xFFFFFFFFu;
-	for (int k = lane; k < nD; k += 64) key = min(key, ((unsigned)accums[px.idx + k] << 16) | (unsigned)k);
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, m, 64));
-	if (lane == 0) { disp[pix] = (short)(px.minDisp + (int)(key & 0xFFFFu)); cost[pix] = (unsigned short)(key >> 16); }
 }

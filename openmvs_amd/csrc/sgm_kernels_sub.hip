@@ -1,8 +1,9 @@
-// sgm_kernels_sub.hip -- the three Match kernels for the narrow, ragged disparity ranges of the tSGM loop: a wavefront is split
-// into PW = 64 / LP sub-groups of LP lanes; a sub-group owns one pixel (WTA), one pair of pixels (cost volume) or one line (path aggregation) and loops
-// over ceil(nD / LP) chunks of its disparity range, so a pixel with <= LP disparities costs one pass and the few wide ones cost more.  Same integer /
-// float arithmetic, same order per pixel as the wide kernels of sgm_kernels.hip (and the reference, SemiGlobalMatcher.cpp:874-1301); only the mapping of
-// work to lanes differs.  Included by sgm_engine.hip after sgm_kernels.hip.
+// sgm_kernels_sub.hip -- the Match kernels for the narrow, ragged disparity ranges of the tSGM loop: a wavefront is split
+// into PW = 64 / LP sub-groups of LP lanes; a sub-group owns one pixel (WTA) or one line (path aggregation) and loops over ceil(nD / LP) chunks of its
+// disparity range, so a pixel with <= LP disparities costs one pass and the few wide ones cost more.  The cost volume is sgm_cost_px_kernel's (a lane per
+// pixel suits narrow ranges as it is).  Same integer arithmetic, same order per pixel as the wide kernels of sgm_kernels.hip (and the reference,
+// SemiGlobalMatcher.cpp:986-1301); only the mapping of work to lanes differs.  The 8-lane WTA also serves the wide mapping.  Included by sgm_engine.hip
+// after sgm_kernels.hip.
 #pragma once
 #include "sgm_kernels.hip"
 
@@ -36,80 +37,6 @@ __global__ __launch_bounds__(256) void sgm_wta_sub_kernel(const SGMPixel* __rest
 	if (have && kk == 0) {
 		if (nD <= 0) { disp[pix] = px.minDisp; cost[pix] = 0xFFFF; }
 		else { disp[pix] = (short)(px.minDisp + (int)(key & 0xFFFFu)); cost[pix] = (unsigned short)(key >> 16); }
-	}
-}
-
-// ---- cost volume: one pair of horizontally adjacent pixels per sub-group ------------------------------------------------------------------------
-template <int LP>
-__global__ __launch_bounds__(256, 2) void sgm_cost_sub_kernel(const unsigned char* __restrict__ colorL, const float* __restrict__ grayL,
-		const float* __restrict__ grayR, int w, int h, int vw, int vh, const SGMPixel* __restrict__ pixels,
-		const float4* __restrict__ setup, unsigned char* __restrict__ costs) {
-	constexpr int PW = 64 / LP;
-	__shared__ float4 s_w[4][PW][SGM_NT + 1];                          // (wA, wB, wA*(vA-meanA), wB*(vB-meanB)) per tap, per pair of the wave
-	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane / LP, kk = lane % LP;
-	const int ppr = (vw + 1) >> 1;                                     // pairs per row
-	const long nPairs = (long)ppr * vh;
-	const long pair0 = ((long)blockIdx.x * 4 + wave) * PW;
-	if (pair0 >= nPairs) return;                                       // (no workgroup barrier below: each wave owns its LDS rows)
-	// weights of the PW pairs of this wave: PW * 49 entries spread over the 64 lanes
-	for (int e = lane; e < PW * SGM_NT; e += 64) {
-		const int s = e / SGM_NT, t = e % SGM_NT;
-		const long pr = pair0 + s;
-		float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-		if (pr < nPairs) {
-			const int row = (int)(pr / ppr), colA = (int)(pr % ppr) * 2;
-			const long pixA = (long)row * vw + colA;
-			const bool hasB = colA + 1 < vw;
-			const SGMPixel pa = pixels[pixA];
-			const bool onA = pa.maxDisp > pa.minDisp;
-			bool onB = false;
-			if (hasB) { const SGMPixel pb = pixels[pixA + 1]; onB = pb.maxDisp > pb.minDisp; }
-			const int ux = colA + SGM_HW, uy = row + SGM_HW, i = t / 7 - SGM_HW, j = t % 7 - SGM_HW;
-			if (onA) { o.x = sgm_weight(colorL, w, ux, uy, i, j); o.z = o.x * (grayL[(size_t)(uy + i) * w + (ux + j)] - setup[pixA].y); }
-			if (onB) { o.y = sgm_weight(colorL, w, ux + 1, uy, i, j); o.w = o.y * (grayL[(size_t)(uy + i) * w + (ux + 1 + j)] - setup[pixA + 1].y); }
-		}
-		s_w[wave][s][t] = o;
-	}
-	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	const long pair = pair0 + sub;
-	const bool have = pair < nPairs;
-	const int row = have ? (int)(pair / ppr) : 0, colA = have ? (int)(pair % ppr) * 2 : 0;
-	const long pixA = (long)row * vw + colA;
-	const bool hasB = have && colA + 1 < vw;
-	SGMPixel pxA, pxB; pxA.idx = 0; pxA.minDisp = 0; pxA.maxDisp = 0; pxA.pad = 0; pxB = pxA;
-	if (have) pxA = pixels[pixA];
-	if (hasB) pxB = pixels[pixA + 1];
-	const int nDA = pxA.maxDisp > pxA.minDisp ? pxA.maxDisp - pxA.minDisp : 0;
-	const int nDB = pxB.maxDisp > pxB.minDisp ? pxB.maxDisp - pxB.minDisp : 0;
-	const int ux = colA + SGM_HW, uy = row + SGM_HW;
-	const float4 sA = have ? setup[pixA] : make_float4(1.f, 0.f, 0.f, 0.f);
-	const float4 sB = hasB ? setup[pixA + 1] : make_float4(1.f, 0.f, 0.f, 0.f);
-	const int nDmax = nDA > nDB ? nDA : nDB;
-#pragma unroll 1
-	for (int k = kk; k < nDmax; k += LP) {
-		asm volatile("" ::: "memory");
-		const int dA = pxA.minDisp + k, dB = pxB.minDisp + k;
-		const bool actA = k < nDA, actB = k < nDB;
-		const bool inA = actA && !(ux - SGM_HW + dA < 0 || ux + SGM_HW + dA >= w);       // all taps inside the right image (:954-957)
-		const bool inB = actB && !(ux + 1 - SGM_HW + dB < 0 || ux + 1 + SGM_HW + dB >= w);
-		const int cA = inA ? ux + dA : SGM_HW, cB = inB ? ux + 1 + dB : SGM_HW;
-		sgm_v2f sum = {0.f, 0.f}, sumSq = {0.f, 0.f}, nom = {0.f, 0.f};
-		int n = 0;
-		for (int i = -SGM_HW; i <= SGM_HW; ++i) {
-			const float* rowA = grayR + (size_t)(uy + i) * w + cA;
-			const float* rowB = grayR + (size_t)(uy + i) * w + cB;
-#pragma unroll
-			for (int j = -SGM_HW; j <= SGM_HW; ++j) {
-				const sgm_v2f f = {rowA[j], rowB[j]};
-				const float4 pw = s_w[wave][sub][n++];
-				const sgm_v2f pww = {pw.x, pw.y}, pwt = {pw.z, pw.w};
-				const sgm_v2f fw = f * pww;
-				sum += fw; sumSq += f * fw; nom += f * pwt;
-			}
-		}
-		if (actA) costs[pxA.idx + (unsigned)k] = inA ? sgm_cost_of(sum.x, sumSq.x, nom.x, sA.x, sA.z) : (unsigned char)255;
-		if (actB) costs[pxB.idx + (unsigned)k] = inB ? sgm_cost_of(sum.y, sumSq.y, nom.y, sB.x, sB.z) : (unsigned char)255;
 	}
 }
 

@@ -62,3 +62,12 @@ def test_product_never_imports_the_oracle():
             if f.endswith((".py", ".hip", ".h", ".hpp", ".cpp")):
                 s = open(os.path.join(dp, f), errors="ignore").read()
                 assert "pyoracle" not in s and "pm_oracle" not in s.replace("oracle/pm_oracle.cpp", "") and "libpm_oracle" not in s, f
+
+
+def test_the_libraries_read_no_environment_variable():
+    """Every route of the engines is chosen by the input or through the ABI (pmhip_set_tuning, sgmhip_set_sub_group_kernels): a switch read from the
+    environment is one no test of this suite can flip inside its process."""
+    for d in (os.path.join(ROOT, "openmvs_amd", "csrc"), os.path.join(ROOT, "include")):
+        for dp, _, fs in os.walk(d):
+            for f in fs:
+                assert "getenv" not in open(os.path.join(dp, f), errors="ignore").read(), os.path.join(dp, f)

@@ -56,19 +56,37 @@ def test_uniform_range_path_kernel(matcher, w, h, dmin, dmax):
     _check(matcher, lb, lg, rg, px, n, mx)
 
 
-def test_uniform_ranges_with_penalties_above_a_byte(matcher):
+# (w, h, kind, dmin, dmax, seed of the image pair): what each reaches in the wide mapping when the penalties do not fit a byte
+ABOVE_A_BYTE_UNIFORM = [(120, 70, "uniform", -2, 46, 77),       # sgm_path_uniform_kernel: even count, one entry per lane
+                        (150, 90, "uniform", 0, 33, 150),       # odd count
+                        (203, 71, "uniform", 0, 70, 203),       # even count, two entries per lane
+                        (90, 160, "uniform", -3, 100, 90),      # odd count, two entries per lane
+                        (80, 20, "uniform", -128, 128, 80),     # sgm_path_kernel, NK = 4: a uniform range too wide for the register-resident kernel
+                        (128, 80, "ragged", -4, 100, 128)]      # NK = 2
+ABOVE_A_BYTE_RAGGED = [(97, 65, "ragged", -5, 40, 97),          # NK = 1; sub-group mapping: line buffers of 64 disparities
+                       (120, 90, "ragged", 0, 200, 120),        # NK = 4; line buffers of 256
+                       (230, 100, "holes", -2, 12, 230)]        # long invalid runs
+
+
+@pytest.mark.parametrize("lanes,w,h,kind,dmin,dmax,seed", [(0,) + c for c in ABOVE_A_BYTE_UNIFORM + ABOVE_A_BYTE_RAGGED] +
+                         [(lanes,) + c for lanes in (8, 16, 32) for c in ABOVE_A_BYTE_RAGGED])
+def test_uniform_ranges_with_penalties_above_a_byte(matcher, lanes, w, h, kind, dmin, dmax, seed):
     """The atomic-free aggregation records best - min Lp <= P2 in a byte per direction; a penalty table with entries above 255 must take the u16 atomic sums instead
-    (same integers as the oracle either way)."""
-    w, h = 120, 70
-    lb, lg, rg = sc.stereo_pair(w, h, 5, seed=77)
-    px, n, mx = sc.ranges(w, h, "uniform", -2, 46)
+    (same integers as the oracle either way).  The penalties are the only thing that selects those routes -- the atomic instantiations of the three path kernels
+    (sgm_path_uniform_kernel, sgm_path_kernel, sgm_path_sub_kernel with line buffers for 64 and 256 disparities) and the winner-take-all over the u16 sums
+    (sgm_wta_sub_kernel, 8 lanes per pixel in the wide mapping, `lanes` in the sub-group mapping) -- so every one of them is reached here: uniform, ragged and
+    masked ranges in the wide mapping (lanes = 0), the ragged and masked ones again with each sub-group width."""
+    lb, lg, rg = sc.stereo_pair(w, h, 5, seed=seed)
+    px, n, mx = sc.ranges(w, h, kind, dmin, dmax, seed=h)
     saved = matcher.P2s.copy()
+    matcher.set_sub_group_kernels(lanes)
     try:
         matcher.P2s = np.minimum(saved.astype(np.int64) * 40 + 200, 3000).astype(np.uint16)
         assert int(matcher.P2s.max()) > 255
         _check(matcher, lb, lg, rg, px, n, mx)
     finally:
         matcher.P2s = saved
+        matcher.set_sub_group_kernels(False)
 
 
 def test_uniform_premise_is_checked(matcher):
