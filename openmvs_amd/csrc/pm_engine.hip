@@ -14,6 +14,7 @@
 #include "pm_cloud_filter.hip"
 #include "pm_image.hip"
 #include "hip_buf.h"
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -112,12 +112,19 @@ int pmhip_scene_gap_interpolation(pmhip_engine* e, const int32_t* viewIds, int n
 int pmhip_scene_remove_small_segments(pmhip_engine* e, const int32_t* viewIds, int nViews, uint32_t nSpeckleSize, float fDepthDiffThreshold) {
 	if (!e || !viewIds || nViews <= 0) return PMHIP_E_ARG;
 	HIPCHK(e, hipSetDevice(e->device));
-	int nmax = 0;
-	for (int b = 0; b < nViews; ++b) { if (viewIds[b] < 0 || viewIds[b] >= e->nImages) return PMHIP_E_ARG; nmax = std::max(nmax, (int)e->vpix(viewIds[b])); }
-	const int cap = nmax; // asymmetric edges are rare; n pairs is far more than ever needed
+	int nmax = 0, cap = 0;
+	for (int b = 0; b < nViews; ++b) {
+		if (viewIds[b] < 0 || viewIds[b] >= e->nImages) return PMHIP_E_ARG;
+		const int vw = e->vw(viewIds[b]), vh = e->vh(viewIds[b]);
+		nmax = std::max(nmax, (int)e->vpix(viewIds[b])); cap = std::max(cap, (int)std::min<long long>(2LL * vw * vh - vw - vh, INT_MAX / 2));   // (2 * ne is an int below)
+	}
+	// A 4-connected w x h map has 2wh - w - h neighbouring pairs and each is one-directional in at most one direction, so the edge list of the largest view
+	// cannot outgrow `cap` pairs (a geometric ramp with a ratio at the threshold fills it: every pair is asymmetric and every pixel its own component).
+	// `ovr` first receives the sizes of the 2 * ne edge ends, then one (root, value) pair for each of the <= min(2 * ne, n) components the edges touch.
+	const size_t nOvr = 2 * (size_t)std::max(std::max(cap, nmax), 1);
 	DevBuf<int> parent, size, edges, nEdges, ovr;
 	HIPCHK(e, parent.alloc(nmax)); HIPCHK(e, size.alloc(nmax));
-	HIPCHK(e, edges.alloc(2 * (size_t)cap)); HIPCHK(e, nEdges.alloc(1)); HIPCHK(e, ovr.alloc(2 * (size_t)cap));
+	HIPCHK(e, edges.alloc(2 * (size_t)std::max(cap, 1))); HIPCHK(e, nEdges.alloc(1)); HIPCHK(e, ovr.alloc(nOvr));
 	const float th = fDepthDiffThreshold * 0.7f;
 	int rc = 0;
 	std::vector<int> hedges, hsize;
@@ -133,7 +140,7 @@ int pmhip_scene_remove_small_segments(pmhip_engine* e, const int32_t* viewIds, i
 		hipLaunchKernelGGL(pmf_cc_asym_kernel, dim3(gx), dim3(256), 0, e->stream, D, parent, vw, vh, th, edges, nEdges, cap);
 		int ne = 0;
 		if (hipMemcpyAsync(&ne, nEdges, sizeof(int), hipMemcpyDeviceToHost, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) { rc = PMHIP_E_HIP; break; }
-		if (ne > cap) { e->err = "remove_small_segments: asymmetric edge list overflow"; rc = PMHIP_E_HIP; break; }
+		if (ne > cap) { e->err = "remove_small_segments: asymmetric edge list overflow"; rc = PMHIP_E_HIP; break; }   // a guard: unreachable by the bound above
 		if (ne > 0) {
 			// replay the reference's seed order on the quotient graph of components linked by one-directional edges
 			hedges.resize(2 * (size_t)ne); hsize.resize(2 * (size_t)ne);

@@ -134,6 +134,20 @@ def test_remove_small_segments_reformulation_equals_the_sequential_region_growin
         with np.errstate(divide="ignore", invalid="ignore"):
             n_asym_cases += int((((np.abs(a - b) / a < th) != (np.abs(a - b) / b < th)) & (a > 0) & (b > 0)).sum())
     assert n_asym_cases > 50          # the test really exercises one-directional edges
+    # the ramps of tests/post_filter_cases.py: every neighbouring pair one-directional (a quotient graph of 2wh - w - h edges over n singletons), and
+    # columns linked by one-directional edges (segment sizes are sums over the replay); 13 x 9, so a column has 9 pixels and a pair of columns 18
+    from tests import post_filter_cases as cases
+    w, h = 13, 9
+    ramps = [m for m in cases.segment_maps(w, h, 0.01) if "ramp" in m[0] or "xpairs" in m[0]]
+    assert [m[0] for m in ramps] == ["ramp_rising", "ramp_falling", "xramp_rising", "xramp_falling", "xpairs_down", "xpairs_up"]
+    for name, depth, claim in ramps:
+        share = cases.asymmetric_share(depth, th)
+        assert (share == 1.0) if name.startswith("ramp") else (0 < share < 1), (name, share)
+        normal = np.zeros((h, w, 3), np.float32); normal[..., 2] = -1; conf = np.full((h, w), 0.5, np.float32)
+        for speckle in (0, 1, 2, 9, 10, 18, 19, 117, 118):
+            od, on, oc = po.remove_small_segments(depth, normal, conf, nSpeckleSize=speckle)
+            assert int((od > 0).sum()) == claim(speckle), (name, speckle)
+            assert np.array_equal(_reformulated_remove_small_segments(depth, speckle, th), od == 0), (name, speckle)
 
 
 def test_remove_small_segments_basic():

@@ -291,6 +291,35 @@ def test_gap_interpolation_is_the_reference_function(seed, gap, th):
     assert ((d == 0) & (a[0] > 0)).sum() > (20 if gap > 1 else 0)               # it filled something
 
 
+# The adversarial maps of tests/post_filter_cases.py are judged by the oracle alone on the emulator and on the device: what it does with NaN, +inf and negative
+# depths, with gaps on a border and with chains of one-directional edges has to be what the reference's own text does.
+@pytest.mark.parametrize("size", [(67, 37), (3, 70), (70, 3)], ids=lambda s: "%dx%d" % s)
+def test_remove_small_segments_on_adversarial_maps_is_the_reference_function(size):
+    from tests import post_filter_cases as cases
+    n = 0
+    for fth in cases.SEGMENT_THRESHOLDS:
+        for k, (name, d, claim) in enumerate(cases.segment_maps(size[0], size[1], fth)):
+            nrm, cnf = cases.normals_and_conf(d, 100 + k)
+            for sz in cases.SPECKLE_SIZES:
+                a = po.remove_small_segments(d, nrm, cnf, nSpeckleSize=sz, fDepthDiffThreshold=fth)
+                b = pr.ref_remove_small_segments(d, nrm, cnf, nSpeckleSize=sz, fDepthDiffThreshold=fth)
+                cases.same(a, b, "RemoveSmallSegments %s nSpeckleSize %d fDepthDiffThreshold %g" % (name, sz, fth))
+                n += 1
+    assert n >= 11 * 7 * 2
+
+
+@pytest.mark.parametrize("size", [(67, 37), (3, 70), (70, 3)], ids=lambda s: "%dx%d" % s)
+def test_gap_interpolation_on_adversarial_maps_is_the_reference_function(size):
+    from tests import post_filter_cases as cases
+    for trial in range(30):
+        d, nrm, cnf, exact, steps = cases.gap_map(size[0], size[1], trial)
+        for gap in cases.GAP_SIZES:
+            for fth in cases.GAP_THRESHOLDS:
+                a = po.gap_interpolation(d, nrm, cnf, nIpolGapSize=gap, fDepthDiffThreshold=fth)
+                b = pr.ref_gap_interpolation(d, nrm, cnf, nIpolGapSize=gap, fDepthDiffThreshold=fth)
+                cases.same(a, b, "GapInterpolation map %d nIpolGapSize %d fDepthDiffThreshold %g" % (trial, gap, fth))
+
+
 # ---- the cross-view filter: DepthMapsData::FilterDepthMap (SceneDensify.cpp:1049-1299) -----------------------------------------------------------
 @pytest.fixture(scope="module")
 def estimated(scene):
