@@ -1,5 +1,7 @@
 // pm_band.hip -- the per-pixel visit (ProcessPixel, DepthMap.cpp:630-852) with its state in LDS, and the sweep kernel of large batches built on it:
-// pm_sweep2_kernel, one launch per anti-diagonal, G lanes per pixel and VPL source views per lane.  (The file name is historical: round 3's resident "band"
+// pm_sweep2_kernel, one launch per anti-diagonal, G lanes per pixel and VPL source views per lane, lanes ordered VIEW-MAJOR: lane = v * PPW + pixel with PPW = 64 / G
+// pixels per wave, so that the four lanes of a quad are four neighbouring pixels of the anti-diagonal scoring against the SAME source view -- their taps fall on
+// neighbouring entries of one anti-diagonal-major quad image (one or two 64-byte blocks per quad instead of four: DESIGN.md 4.1).  (The file name is historical: round 3's resident "band"
 // kernel -- one launch per sweep iteration with wave-to-wave hand-offs -- lived here; it was bit-exact and slower than per-diagonal launches everywhere it was
 // measured, profiles/README.md, and is gone.)
 #pragma once
@@ -17,16 +19,18 @@
 #define PM_BAND_MINWAVES_PHOTO 4   // the photometric instantiations fit four waves per SIMD (128 VGPRs) without scratch
 #endif
 
-// Per-pixel state of a visit, in LDS.  The G lanes of a pixel all need it and all hold the same values, so one lane writes and all read: what lives in
+// Per-pixel state of a visit, in LDS.  The G lanes of a pixel (PPW lanes apart) all need it and all hold the same values, so one lane writes and all read: what lives in
 // registers while a hypothesis is scored (the long part of a visit) is then only what the scoring itself needs -- the register budget that decides how
 // many waves a SIMD holds.  Accessed through pm_launder() so that the compiler re-reads instead of carrying values across the scoring in registers.
-struct PMPix {
+struct alignas(16) PMPix {
+	float nb[2][5];                            // the two already-updated neighbours: depth, normal, conf.  nb[0] is read once, by the first trip's head (ST_PROP0 comes first for
+	                                           // every pixel); from then on its first 16 bytes hold the four smoothness factors of the hypothesis being scored (pm_pix_sf): lane
+	                                           // row `slot` writes its neighbour's, every lane reads the four at once -- no LDS beyond what the struct took before
 	float depth, nx, ny, nz, conf;             // current estimate (DepthMap.cpp:767-769)
 	float p0, p1, scaleRange, depthRange;      // refinement state (:828-852)
 	int st, it, idxScale, flags;               // flags: bit 0 smooth, bit 1 changed, bit 2 / 3 propagation candidate 0 / 1 exists, bits 8..11 closeMask
 	float hd, hnx, hny, hnz, hp0, hp1;         // hypothesis being scored
 	int hst, pad0;
-	float nb[2][5];                            // the two already-updated neighbours: depth, normal, conf
 	float qX[4][3], qn[4][3];                  // neighborsClose: point and normal of slot k
 	float vx, vy, normSq0, sumW;
 	double X0x, X0y;
@@ -46,49 +50,58 @@ template <class T> __device__ __forceinline__ PM_LDS T* pm_launder(T* p) { PM_LD
 #define PM_LDS
 template <class T> __device__ __forceinline__ T* pm_launder(T* p) { return p; }
 #endif
+static_assert(sizeof(PMPix) == 368, "sixteen of them, the weights and the views' matrices fit a sixteenth of a CU's LDS (tests/test_kernel_resources.py)");
+__device__ __forceinline__ PM_LDS float* pm_pix_sf(PM_LDS PMPix* P) { return P->nb[0]; }
 enum { PMF_SMOOTH = 1, PMF_CHANGED = 2, PMF_POK0 = 4, PMF_POK1 = 8 };
 
-// One ProcessPixel visit (DepthMap.cpp:630-852) of the G lanes of a pixel, shared by the band kernel and the per-diagonal kernel below.
-// n0* / n1*: the two neighbours the sweep has already updated (depth, normal, conf), however the caller obtained them; bok / qxs / qys / qis: the four
+// One ProcessPixel visit (DepthMap.cpp:630-852) of the G lanes of a pixel: lanes g, PPW + g, 2 PPW + g, ... of the wave (g = pixel, v = lane row).
+// What only one lane of a pixel needs from memory only that lane loads (a quad holds four PIXELS now: a load repeated by every lane row would cost four blocks per
+// quad in each row instead of one per pixel): row 0 the pixel's own estimate, prior and mask, rows 0..3 the neighbour of their smoothness slot.
+// n0* / n1*: the two neighbours the sweep has already updated (depth, normal, conf), loaded by lane row 0 / 1 only; bok / qxs / qys / qis: the four
 // neighbour slots (bounds tests, coordinates, map indices).  afterPatch() runs once the visit's loads have been waited for (the band kernel publishes its
 // previous step there).  Result: r* = what the maps hold at this pixel after the visit, wr = it changed.
 template <int G, int VPL, bool GEO, bool BUF, bool TILED>
 __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, const PMImgBuf& rs, uint32_t pass, int sgn, float2* s_wg, PMPix* s_pixg, const double* hotBase,
-		int g, int v, int slot, bool active, int x, int y, int ySafe, size_t idx, const bool* bok, const int* qxs, const int* qys, const size_t* qis, unsigned oldMask,
+		int g, int v, bool active, int x, int y, int ySafe, size_t idx, const bool* bok, const int* qxs, const int* qys, const size_t* qis, unsigned oldMask,
 		float n0D, float n0N0, float n0N1, float n0N2, float n0C, float n1D, float n1N0, float n1N1, float n1N2, float n1C,
 		float& rD, float& rN0, float& rN1, float& rN2, float& rC, bool& wr PM_PROF_ARG) {
 	constexpr int NBD = PM_SRC_HOT + (GEO ? PM_SRC_GEO : 0);
+	constexpr int PPW = 64 / G;
+	const int slot = v & 3;
 	const pm_gf gDepth = pm_globw(t.depth), gNormal = pm_globw(t.normal), gConf = pm_globw(t.conf);
 	const int yTop = ySafe;
 	// ---- what the visit reads from memory: its own estimate, the two not yet updated neighbours, prior, mask (none of it written earlier in this launch) ----
 	float oDepth = 0.f, oNx = 0.f, oNy = 0.f, oNz = 0.f, oConf = 2.f, prior = 0.f;
 	float myD = 0.f, myN0 = 0.f, myN1 = 0.f, myN2 = 1.f;     // depth and normal of my smoothness slot's pixel
 	unsigned char maskByte = 1;
-	if (active) {
-		if (t.prior) prior = pm_glob(t.prior)[idx];
-		if (t.mask != nullptr) maskByte = t.mask[idx];
-		if (slot == 0) { myD = bok[0] ? n0D : 0.f; myN0 = n0N0; myN1 = n0N1; myN2 = n0N2; }
-		else if (slot == 1) { myD = bok[1] ? n1D : 0.f; myN0 = n1N0; myN1 = n1N1; myN2 = n1N2; }
+	if (active && v < 4) {
+		if (v == 0) {
+			if (t.prior) prior = pm_glob(t.prior)[idx];
+			if (t.mask != nullptr) maskByte = t.mask[idx];
+			oDepth = gDepth[idx]; oNx = gNormal[idx * 3]; oNy = gNormal[idx * 3 + 1]; oNz = gNormal[idx * 3 + 2]; oConf = gConf[idx];
+			myD = bok[0] ? n0D : 0.f; myN0 = n0N0; myN1 = n0N1; myN2 = n0N2;
+		}
+		else if (v == 1) { myD = bok[1] ? n1D : 0.f; myN0 = n1N0; myN1 = n1N1; myN2 = n1N2; }
 		else {   // the two neighbours the sweep has not reached yet: the maps hold what the sweep found -- across a tile border (tiled sweeps) that is the snapshot
 			const size_t qi = slot == 2 ? qis[2] : qis[3];
 			const bool old = TILED && ((oldMask >> slot) & 1u);
 			const pm_gcf sD = pm_glob(old ? t.depthOld : t.depth), sN = pm_glob(old ? t.normalOld : t.normal);
 			myD = sD[qi]; myN0 = sN[qi * 3]; myN1 = sN[qi * 3 + 1]; myN2 = sN[qi * 3 + 2];
 		}
-		oDepth = gDepth[idx]; oNx = gNormal[idx * 3]; oNy = gNormal[idx * 3 + 1]; oNz = gNormal[idx * 3 + 2]; oConf = gConf[idx];
 	}
 	float normSq0, sumW;
 	pm_fill_patch<G, true>(t, active, active ? x : PM_HW, active ? y : yTop, v, s_wg, normSq0, sumW);
-	const bool masked = active && maskByte == 0;
-	const bool valid = active && !masked && !(normSq0 < kp.thMagnitudeSq && !(prior > 0));
+	// (lane row 0 holds the pixel's prior and mask: its verdict reaches the other rows through a ballot -- lane g is pixel g's row 0)
+	const bool valid0 = v == 0 && active && maskByte != 0 && !(normSq0 < kp.thMagnitudeSq && !(prior > 0));
+	const bool valid = ((__ballot(valid0) >> g) & 1ull) != 0;
 	if (v == 0) s_wg[PM_NT] = make_float2(prior, prior > 0 ? pm_expf(normSq0 * (-1.f / (1.f * 0.02f))) : 0.f);
 	// ---- the visit's state goes to LDS: current estimate, neighbours, close-neighbour slots (lane `slot` of the first quad writes slot `slot`) ----
 	{
 		PM_LDS PMPix* P = pm_launder(s_pixg);
 		const bool bk = slot == 0 ? bok[0] : slot == 1 ? bok[1] : slot == 2 ? bok[2] : bok[3];
 		const bool okS = valid && bk && myD > 0;
-		const unsigned long long bal = __ballot(okS);   // (ballot of the whole wave; my pixel's four bits -- its lanes v = 0..3 -- are picked here)
-		const unsigned closeMask = (unsigned)((bal >> (g * G)) & 0xFull);
+		const unsigned long long bal = __ballot(okS) >> g;   // (ballot of the whole wave; my pixel's four bits -- its lanes v = 0..3, PPW apart -- are picked here)
+		const unsigned closeMask = (unsigned)((bal & 1ull) | ((bal >> (PPW - 1)) & 2ull) | ((bal >> (2 * PPW - 2)) & 4ull) | ((bal >> (3 * PPW - 3)) & 8ull));
 		if (v < 4) {
 			// TransformPointI2C(Point3(nx, ndepth)) in double then Cast<float>, Camera.h:338-344
 			const int qx = slot == 0 ? qxs[0] : slot == 1 ? qxs[1] : slot == 2 ? qxs[2] : qxs[3];
@@ -107,11 +120,11 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 			enum { ST_PROP0 = 0, ST_DONE = 5 };
 			P->st = valid ? ST_PROP0 : ST_DONE; P->it = 0; P->idxScale = 0;
 			P->flags = PMF_SMOOTH | ((closeMask & 1u) ? PMF_POK0 : 0) | ((closeMask & 2u) ? PMF_POK1 : 0) | (int)(closeMask << 8);
-			P->nb[0][0] = n0D; P->nb[0][1] = n0N0; P->nb[0][2] = n0N1; P->nb[0][3] = n0N2; P->nb[0][4] = n0C;
-			P->nb[1][0] = n1D; P->nb[1][1] = n1N0; P->nb[1][2] = n1N1; P->nb[1][3] = n1N2; P->nb[1][4] = n1C;
 		}
-		if (v < 2)   // InterpolatePixel's x1 (DepthMap.cpp:915-959): lane 0 the same-row neighbour, lane 1 the same-column one
+		if (v < 2) {   // the already-updated neighbour and InterpolatePixel's x1 (DepthMap.cpp:915-959): lane row 0 the same-row neighbour, row 1 the same-column one
+			P->nb[v][0] = v == 0 ? n0D : n1D; P->nb[v][1] = v == 0 ? n0N0 : n1N0; P->nb[v][2] = v == 0 ? n0N1 : n1N1; P->nb[v][3] = v == 0 ? n0N2 : n1N2; P->nb[v][4] = v == 0 ? n0C : n1C;
 			P->x1[v] = v == 0 ? (float)(((double)(x + sgn) - t.cx) / t.fx) : (float)(((double)(y + sgn) - t.cy) / t.fy);
+		}
 		// the refinement draws of iterations v, v + G, ...: one Philox per lane and round instead of one per hypothesis by every lane
 		const unsigned nd = min((unsigned)PM_NDRAW, kp.nRandomIters);
 		for (unsigned it0 = 0; it0 < nd; it0 += G) {
@@ -128,6 +141,7 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 	enum { ST_PROP0 = 0, ST_PROP1 = 1, ST_DECIDE = 2, ST_RAND = 3, ST_REFINE = 4, ST_DONE = 5 };
 	const uint32_t k1 = t.k1base + pass;
 	for (;;) {
+		PM_CENSUS_TRIP();
 		bool need = false;
 		float hd = 0.f, hnx = 0.f, hny = 0.f, hnz = 1.f;
 		{	// -- next hypothesis of my pixel (every lane of the group computes the same; lane 0 records it)
@@ -192,7 +206,7 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 					if (!pm_in_range(ndepth, t.dMin, t.dMax)) continue;
 					hp0 = p0 + (kp.angle1Range * scaleRange) * e1;
 					hp1 = p1 + (kp.angle2Range * scaleRange) * e2;
-					pm_dir2normal_quad(hp0, hp1, v, hnx, hny, hnz);
+					pm_dir2normal_vm<PPW>(hp0, hp1, v, hnx, hny, hnz);
 					if (hnx * vx + hny * vy + hnz * vz >= 0) continue;
 					hd = ndepth;
 					need = true; hst = ST_REFINE;
@@ -211,12 +225,13 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 		const unsigned long long needBal = __ballot(need);
 		if (needBal == 0ull) break;
 		PM_TICK(1); PM_COUNT(8, __popcll(needBal)); PM_HIST(__popcll(needBal) / G);
-		// -- smoothness factors of the hypothesis plane w.r.t. the close neighbours, DepthMap.cpp:524-533, one neighbour per lane
-		float sf0, sf1, sf2, sf3;
+		// -- smoothness factors of the hypothesis plane w.r.t. the close neighbours, DepthMap.cpp:524-533, one neighbour per lane row 0..3; they reach the pixel's other
+		//    lanes through its state in LDS: one 4-byte write here, one 16-byte read per view where the score takes them (pm_score_view) -- fewer instructions than four
+		//    ds_bpermute_b32 with their lane addresses, and no registers held across the tap rows
 		{
-			const PM_LDS PMPix* P = pm_launder(s_pixg);
+			PM_LDS PMPix* P = pm_launder(s_pixg);
 			const int flags = P->flags;
-			const bool on = need && (flags & PMF_SMOOTH) && ((flags >> (8 + slot)) & 1);
+			const bool on = need && v < 4 && (flags & PMF_SMOOTH) && ((flags >> (8 + slot)) & 1);
 			float myF = 1.f;
 			if (on) {
 				const float vx = P->vx, vy = P->vy;
@@ -230,7 +245,8 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 				const float factorNormal = pm_expf((ac * ac) * kp.smoothSigmaNormal);
 				myF = (1.f - kp.smoothBonusDepth * factorDepth) * (1.f - kp.smoothBonusNormal * factorNormal);
 			}
-			sf0 = pm_quad_bcast<0>(myF); sf1 = pm_quad_bcast<1>(myF); sf2 = pm_quad_bcast<2>(myF); sf3 = pm_quad_bcast<3>(myF);
+			if (v < 4) pm_pix_sf(P)[slot] = myF;
+			__builtin_amdgcn_wave_barrier();
 		}
 		PM_TICK(2);
 		// -- score against my source view(s)
@@ -241,13 +257,15 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 			for (int u = 0; u < VPL; ++u) {
 				const int vw = v + u * G;
 				if (need && vw < t.nSrc) {
-					const float s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, sf0, sf1, sf2, sf3, 0.f,
-						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr);
+					PM_CENSUS_VIEW(t.w, G, u);
+					const float s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, 1.f, 1.f, 1.f, 1.f, 0.f,
+						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P));
+					PM_CENSUS_VIEW_END();
 					if (s1 < sc) { sc2 = sc; sc = s1; } else if (s1 < sc2) sc2 = s1;
 				}
 			}
 		}
-		const float nconf = pm_aggregate<G>(sc, t.nSrc, kp.thRobust, sc2);
+		const float nconf = pm_aggregate_vm<G>(sc, t.nSrc, kp.thRobust, sc2);
 		{	// -- accept (DepthMap.cpp:794-799, :784-793, :843-851)
 			PM_LDS PMPix* P = pm_launder(s_pixg);
 			if (need && v == 0 && P->conf > nconf) {
@@ -271,8 +289,9 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 
 // One launch of a sweep (PMStep): in place; the two already-updated neighbours are read back from the maps (the previous launch wrote them); launches on one stream order the
 // anti-diagonals.  TILED: the opt-in tiled sweeps -- pixels numbered tile by tile, neighbours across a tile border read from the snapshot of the sweep's start.
-// (Measured and dropped in round 4: "view-major" lanes -- lane = view * pixels-per-wave + pixel, so that the four lanes of a quad read adjacent entries of one quad
-// image -- 43.1 vs 42.6 Mpix/s at 100 views, 28.1 vs 28.3 at 25: the order in which a wave's addresses reach the vector L1 is not what bounds the kernel.
+// (Lane order: round 4 measured view-major lanes at +1.2 % (43.1 vs 42.6 Mpix/s at 100 views) when the arithmetic was the bound, and dropped them.  With the texture-address
+// unit as the bound (round 6) the census of tools/gather_census.py counts 0.46-0.47 of the pixel-major order's 64-byte blocks per quad, and the device A/B gives +3.0 % at
+// 100 views, +2.0 % at 50, +-0 at 25: profiles/lane_order_census.txt, profiles/lane_order_ab.log, DESIGN.md 4.1.
 // Round 6: 32 pixels resident per wave with a per-trip choice of the 16 that score, and wide tail trips -- pixels still refining get twice the lanes when at most half of the
 // wave's pixels take part: bit-identical, -14 % and +-0 on the benchmark, whose every pixel scores exactly 8 hypotheses: there is no lock-step loss to recover there;
 // profiles/r06_resident32_wide_trips_experiment.diff, profiles/r06_call3/ab_100.log.)
@@ -298,7 +317,7 @@ __global__ __launch_bounds__(64, (GEO ? PM_BAND_MINWAVES : PM_BAND_MINWAVES_PHOT
 	const PMImgBuf rs = pm_make_imgbuf(t);
 	const int lane = threadIdx.x;
 	for (int i = lane; i < NV * NBD; i += 64) s_src[i] = ((const double*)&t.src[i / NBD])[i % NBD];
-	const int g = lane / G, v = lane % G, slot = v & 3;
+	const int g = lane % PPW, v = lane / PPW;   // view-major: a quad of lanes = four neighbouring pixels, one source view
 	const int w = t.w, h = t.h;
 	const PMStepPix sp = pm_step_pixel<TILED>(st, w, h, (int)vbx * PPW + g);
 	const bool active = sp.active;
@@ -316,21 +335,21 @@ __global__ __launch_bounds__(64, (GEO ? PM_BAND_MINWAVES : PM_BAND_MINWAVES_PHOT
 	}
 	const pm_gf gDepth = pm_globw(t.depth), gNormal = pm_globw(t.normal), gConf = pm_globw(t.conf);
 	float n0D = 0.f, n0N0 = 0.f, n0N1 = 0.f, n0N2 = 0.f, n0C = 2.f, n1D = 0.f, n1N0 = 0.f, n1N1 = 0.f, n1N2 = 0.f, n1C = 2.f;
-	if (active) {
+	if (active && v < 2) {   // lane row 0 loads the same-row neighbour, row 1 the same-column one (pm_visit publishes them through the pixel's state)
 		const size_t q0 = qis[0], q1 = qis[1];
 		if (TILED) {   // across a tile border: as the sweep found them
 			const pm_gcf nD0 = pm_glob((sp.oldMask & 1u) ? t.depthOld : t.depth), nN0 = pm_glob((sp.oldMask & 1u) ? t.normalOld : t.normal), nC0 = pm_glob((sp.oldMask & 1u) ? t.confOld : t.conf);
 			const pm_gcf nD1 = pm_glob((sp.oldMask & 2u) ? t.depthOld : t.depth), nN1 = pm_glob((sp.oldMask & 2u) ? t.normalOld : t.normal), nC1 = pm_glob((sp.oldMask & 2u) ? t.confOld : t.conf);
-			n0D = nD0[q0]; n0N0 = nN0[q0 * 3]; n0N1 = nN0[q0 * 3 + 1]; n0N2 = nN0[q0 * 3 + 2]; n0C = nC0[q0];
-			n1D = nD1[q1]; n1N0 = nN1[q1 * 3]; n1N1 = nN1[q1 * 3 + 1]; n1N2 = nN1[q1 * 3 + 2]; n1C = nC1[q1];
+			if (v == 0) { n0D = nD0[q0]; n0N0 = nN0[q0 * 3]; n0N1 = nN0[q0 * 3 + 1]; n0N2 = nN0[q0 * 3 + 2]; n0C = nC0[q0]; }
+			else { n1D = nD1[q1]; n1N0 = nN1[q1 * 3]; n1N1 = nN1[q1 * 3 + 1]; n1N2 = nN1[q1 * 3 + 2]; n1C = nC1[q1]; }
 		} else {
-			n0D = gDepth[q0]; n0N0 = gNormal[q0 * 3]; n0N1 = gNormal[q0 * 3 + 1]; n0N2 = gNormal[q0 * 3 + 2]; n0C = gConf[q0];
-			n1D = gDepth[q1]; n1N0 = gNormal[q1 * 3]; n1N1 = gNormal[q1 * 3 + 1]; n1N2 = gNormal[q1 * 3 + 2]; n1C = gConf[q1];
+			if (v == 0) { n0D = gDepth[q0]; n0N0 = gNormal[q0 * 3]; n0N1 = gNormal[q0 * 3 + 1]; n0N2 = gNormal[q0 * 3 + 2]; n0C = gConf[q0]; }
+			else { n1D = gDepth[q1]; n1N0 = gNormal[q1 * 3]; n1N1 = gNormal[q1 * 3 + 1]; n1N2 = gNormal[q1 * 3 + 2]; n1C = gConf[q1]; }
 		}
 	}
 	__syncthreads();
 	float rD, rN0, rN1, rN2, rC; bool wr;
-	pm_visit<G, VPL, GEO, BUF, TILED>(t, kp, rs, pass, sgn, s_w[g], &s_pix[g], s_src, g, v, slot, active, x, y, active ? y : PM_HW, active ? idx : (size_t)PM_HW * w + PM_HW, bok, qxs, qys, qis, sp.oldMask,
+	pm_visit<G, VPL, GEO, BUF, TILED>(t, kp, rs, pass, sgn, s_w[g], &s_pix[g], s_src, g, v, active, x, y, active ? y : PM_HW, active ? idx : (size_t)PM_HW * w + PM_HW, bok, qxs, qys, qis, sp.oldMask,
 		n0D, n0N0, n0N1, n0N2, n0C, n1D, n1N0, n1N1, n1N2, n1C, rD, rN0, rN1, rN2, rC, wr PM_PROF_PASS);
 	if (wr && v == 0) { gDepth[idx] = rD; gNormal[idx * 3] = rN0; gNormal[idx * 3 + 1] = rN1; gNormal[idx * 3 + 2] = rN2; gConf[idx] = rC; }
 	PM_PROF_FLUSH();

@@ -247,6 +247,46 @@ __device__ __forceinline__ void pm_dir2normal_quad(float p0, float p1, int v, fl
 	nx = cx * sy; ny = sx * sy; nz = cy;
 }
 
+// ---- view-major lanes (pm_sweep2_kernel, pm_band.hip): lane = v * PPW + pixel, PPW = 64 / G pixels per wave.  The G lanes of a pixel sit PPW apart, so what they
+// exchange crosses DPP rows: through the LDS crossbar (__shfl_xor -> ds_bpermute_b32, which does not pass the texture-address unit), except at PPW = 8, where the
+// partner PPW away is the row rotated by eight.
+template <int PPW> __device__ __forceinline__ float pm_lane_xor(float v, int o = PPW) {
+	if (PPW == 8 && o == 8) return PM_DPP_F(v, 0x128);   // row_ror:8
+	return __shfl_xor(v, o, 64);
+}
+// pm_group_min2 over the lanes PPW, 2 PPW, ... apart (exact, so the pairing does not matter: see there)
+template <int G>
+__device__ __forceinline__ void pm_group_min2_vm(float s, float s2, float& m1, float& m2) {
+	constexpr int PPW = 64 / G;
+	float a = s, b = s2;
+#pragma unroll
+	for (int o = PPW; o < 64; o <<= 1) {
+		const float oa = pm_lane_xor<PPW>(a, o), ob = pm_lane_xor<PPW>(b, o);
+		const float na = pm_minf(a, oa), nb = pm_minf(pm_maxf(a, oa), pm_minf(b, ob)); a = na; b = nb;
+	}
+	m1 = a; m2 = b;
+}
+// pm_aggregate over a view-major group
+template <int G>
+__device__ __forceinline__ float pm_aggregate_vm(float viewScore, int nSrc, float thRobust, float viewScore2) {
+	float m1, m2;
+	pm_group_min2_vm<G>(viewScore, viewScore2, m1, m2);
+	if (nSrc <= 1) return m1;
+	if (m2 >= thRobust) return m1;
+	return (m1 + m2) / 2.f;
+}
+// pm_dir2normal_quad for view-major lanes: even lane rows take p0, odd rows p1, and a lane gets the other angle's sine and cosine from its partner PPW lanes away.
+// Every lane of the pixel must call it (they share the pixel's state, so they do).
+template <int PPW>
+__device__ __forceinline__ void pm_dir2normal_vm(float p0, float p1, int v, float& nx, float& ny, float& nz) {
+	const bool odd = (v & 1) != 0;
+	float s, c;
+	pm_sincosf(odd ? p1 : p0, &s, &c);
+	const float os = pm_lane_xor<PPW>(s), oc = pm_lane_xor<PPW>(c);
+	const float sx = odd ? os : s, cx = odd ? oc : c, sy = odd ? s : os, cy = odd ? c : oc;
+	nx = cx * sy; ny = sx * sy; nz = cy;
+}
+
 // ScorePixelImage for this lane's source view, DepthMap.cpp:465-564.
 // sf[]: the (view-independent) smoothness factors of the up-to-4 close neighbours, in insertion
 // order; exactly 1.f for a neighbour that does not exist or does not take part (DepthMap.cpp:524-533).
@@ -337,7 +377,75 @@ __device__ __forceinline__ unsigned pm_mad24(int a, int b, unsigned c) { unsigne
 typedef float4 pm_f4v;
 struct pm_rsrc { const float4* base; unsigned count; };
 __device__ __forceinline__ pm_rsrc pm_make_rsrc(const void* base, unsigned count) { return pm_rsrc{(const float4*)base, count}; }
+#if defined(PM_GATHER_CENSUS)
+// Census of the tap rows' gathers (tools/gather_census.py; host build only, as PM_DEBUG_REDO below): how many distinct 64-byte blocks (four 16-byte entries) the four lanes
+// of a quad touch in one wave-load of pm_sweep2_kernel.  pm_visit names the wave-load a lane is in -- (trip, view round), then the tap rows in order -- and pm_bufload5
+// records the lane's five entry indices under it; when another workgroup begins (or the process ends) the records of the finished one are grouped into quads, under the
+// shipped view-major lane order and under the pixel-major order it replaced (the same indices, grouped by lane' = pixel * G + v).  Printed per level (image width) at exit.
+#include <algorithm>
+#include <array>
+namespace pm_census {
+struct Rec { unsigned key; unsigned lane; unsigned idx[5]; };
+struct Stat { unsigned long long loads = 0, lanes = 0, blocksVM = 0, blocksPM = 0, quadsVM[5] = {0, 0, 0, 0, 0}; };
+inline std::vector<Rec> recs;
+inline std::map<int, Stat> stats;
+inline unsigned long long wgLaunch = ~0ull; inline unsigned wgX = 0, wgY = 0; inline int wgWidth = 0, wgG = 4;
+inline unsigned trips[64], curKey = 0, curRow = 0; inline bool armed = false;   // armed: inside a pm_score_view call of pm_visit (the init kernel gathers through pm_bufload5 too)
+inline unsigned blocksOfQuads(const std::array<unsigned, 64>& blk, unsigned long long on, unsigned long long* hist) {
+	unsigned total = 0;
+	for (int q = 0; q < 16; ++q) {
+		unsigned seen[4]; int n = 0;
+		for (int l = 4 * q; l < 4 * q + 4; ++l) if ((on >> l) & 1ull) { bool dup = false; for (int k = 0; k < n; ++k) dup = dup || seen[k] == blk[l]; if (!dup) seen[n++] = blk[l]; }
+		total += (unsigned)n; if (hist) hist[n]++;
+	}
+	return total;
+}
+inline void flush() {
+	if (recs.empty()) return;
+	std::stable_sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) { return a.key < b.key; });
+	Stat& s = stats[wgWidth];
+	const int G = wgG, PPW = 64 / G;
+	for (size_t i = 0; i < recs.size();) {
+		size_t j = i; while (j < recs.size() && recs[j].key == recs[i].key) ++j;
+		for (int k = 0; k < 5; ++k) {   // the row's five wave-loads
+			std::array<unsigned, 64> vm{}, pm{}; unsigned long long onVM = 0, onPM = 0;
+			for (size_t r = i; r < j; ++r) {
+				const unsigned l = recs[r].lane, g = l % PPW, v = l / PPW, lp = g * G + v;
+				vm[l] = recs[r].idx[k] >> 2; onVM |= 1ull << l; pm[lp] = recs[r].idx[k] >> 2; onPM |= 1ull << lp;
+			}
+			s.loads++; s.lanes += (unsigned long long)(j - i);
+			s.blocksVM += blocksOfQuads(vm, onVM, s.quadsVM); s.blocksPM += blocksOfQuads(pm, onPM, nullptr);
+		}
+		i = j;
+	}
+	recs.clear();
+}
+inline void report() {
+	flush();
+	for (auto& kv : stats) {
+		const Stat& s = kv.second; const double L = (double)s.loads, Q = 16.0 * L;
+		fprintf(stderr, "gather census: level width %d: %llu tap wave-loads, %.1f active lanes per load; blocks per load: view-major (shipped) %.2f, pixel-major %.2f, ratio %.3f; "
+			"blocks per quad (shipped) %.3f; quads touching 0/1/2/3/4 blocks: %.1f %.1f %.1f %.1f %.1f %%\n", kv.first, s.loads, s.lanes / L, s.blocksVM / L, s.blocksPM / L,
+			(double)s.blocksVM / (double)s.blocksPM, s.blocksVM / Q, 100.0 * s.quadsVM[0] / Q, 100.0 * s.quadsVM[1] / Q, 100.0 * s.quadsVM[2] / Q, 100.0 * s.quadsVM[3] / Q, 100.0 * s.quadsVM[4] / Q);
+	}
+}
+inline void enter() {   // (fibers of one workgroup run to the end before the next workgroup starts: a change of workgroup closes the previous one's records)
+	static bool reg = false; if (!reg) { reg = true; atexit(report); }
+	if (wgLaunch != hipemu::launches || wgX != blockIdx.x || wgY != blockIdx.y) { flush(); wgLaunch = hipemu::launches; wgX = blockIdx.x; wgY = blockIdx.y; for (unsigned& t : trips) t = 0; }
+}
+inline void trip() { enter(); trips[threadIdx.x & 63]++; }
+inline void view(int width, int G, int u) { wgWidth = width; wgG = G; curKey = (trips[threadIdx.x & 63] * 8u + (unsigned)u) * 8u; curRow = 0; armed = true; }
+inline void viewEnd() { armed = false; }
+inline void note(unsigned i0, unsigned i1, unsigned i2, unsigned i3, unsigned i4) { if (armed) recs.push_back(Rec{curKey + curRow++, threadIdx.x & 63u, {i0, i1, i2, i3, i4}}); }
+}
+#define PM_CENSUS_TRIP() pm_census::trip()
+#define PM_CENSUS_VIEW(width, G, u) pm_census::view((width), (G), (u))
+#define PM_CENSUS_VIEW_END() pm_census::viewEnd()
+#endif
 __device__ __forceinline__ void pm_bufload5(pm_f4v& q0, pm_f4v& q1, pm_f4v& q2, pm_f4v& q3, pm_f4v& q4, unsigned i0, unsigned i1, unsigned i2, unsigned i3, unsigned i4, pm_rsrc r) {
+#if defined(PM_GATHER_CENSUS)
+	pm_census::note(i0, i1, i2, i3, i4);
+#endif
 	const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 	q0 = i0 < r.count ? r.base[i0] : z; q1 = i1 < r.count ? r.base[i1] : z; q2 = i2 < r.count ? r.base[i2] : z; q3 = i3 < r.count ? r.base[i3] : z; q4 = i4 < r.count ? r.base[i4] : z;
 }
@@ -345,6 +453,11 @@ template <int LEFT> __device__ __forceinline__ void pm_bufwait5(pm_f4v&, pm_f4v&
 __device__ __forceinline__ unsigned pm_mad24(int a, int b, unsigned c) { return (unsigned)(((unsigned)a & 0xffffffu) * ((unsigned)b & 0xffffffu)) + c; }   // wraps as the hardware's low 32 bits do
 #endif
 
+#ifndef PM_CENSUS_TRIP
+#define PM_CENSUS_TRIP()
+#define PM_CENSUS_VIEW(width, G, u)
+#define PM_CENSUS_VIEW_END()
+#endif
 // what the buffer path of the tap rows needs, wave-uniform: the descriptor of the level's quad buffer
 struct PMImgBuf { pm_rsrc rs; };
 __device__ __forceinline__ PMImgBuf pm_make_imgbuf(const PMTask& t) {
@@ -493,6 +606,7 @@ __device__ __forceinline__ void pm_taps_fast(const PMImgBuf& rs, unsigned qbase,
 // MODE 1: optimistic rows from the view's quad image through its own pointer;  MODE 2: optimistic rows from the level's quad buffer (pm_tap_row_fast<true>).
 // PF: the pixel's low-resolution prior and its blend factor exp(normSq0 * sigma) sit in the spare 26th entry of the pixel's weight row in LDS (written once per
 // visit by the sweep kernels) instead of in two registers that are live across the whole hypothesis loop.
+// sfp: where the four factors are read from instead, at the point where the score takes them (16-byte aligned).
 // hot / geoTab: the hot and geometric blocks of `s` (PMSrcView), in HBM (init kernel) or in the wave's LDS copy (sweep kernels); the image size and the view's
 // first entry in the level's quad buffer travel with the homography entries.
 // EARLY: test two opposite corner taps before any load (pm_sweep2_kernel, whose launches fill the GPU and run into the texture-address unit; the speculative kernels of the
@@ -502,7 +616,7 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		int x, int y, double X0x, double X0y, float normSq0, float sumW, const float2* wts,
 		float depth, float nx, float ny, float nz,
 		float sf0, float sf1, float sf2, float sf3, float prior,
-		const double* hot, const double* geoTab, const PMImgBuf& rs PM_PROF_ARG, const double* rpre = nullptr)
+		const double* hot, const double* geoTab, const PMImgBuf& rs PM_PROF_ARG, const double* rpre = nullptr, const float* sfp = nullptr)
 {
 	const int sw = ((const int*)(hot + 12))[0], sh = ((const int*)(hot + 12))[1];
 	float H[9];
@@ -604,6 +718,7 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 	const float ncc = pm_clampf(num / pm_sqrtf(nrmSq), -1.f, 1.f);
 	float score = 1.f - ncc;
 	// (a factor of a neighbour that does not take part is exactly 1.f, and x * 1.f == x: no test needed, DepthMap.cpp:524-533)
+	if (sfp) { sf0 = sfp[0]; sf1 = sfp[1]; sf2 = sfp[2]; sf3 = sfp[3]; }   // (pm_sweep2_kernel: the factors wait in the pixel's LDS state instead of in four registers across the tap rows)
 	score *= sf0; score *= sf1; score *= sf2; score *= sf3;
 	if (GEO) {
 		// geometric consistency, DepthMap.cpp:535-551

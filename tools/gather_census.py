@@ -1,0 +1,67 @@
+"""Census of the sweep kernel's tap gathers on the wave64 emulator (no GPU needed): for the shipped lane order of pm_sweep2_kernel, how many distinct 64-byte blocks
+(four 16-byte quad-image entries) the four lanes of a quad touch in one tap wave-load -- what the texture-address unit is paid by.
+
+    python tools/gather_census.py [WxH ...]          # default: 512x288 960x540
+
+Builds the emulated library (tests/emu.py's recipe) with -DPM_GATHER_CENSUS -- a hook in the HOST branch of pm_bufload5 and two markers in pm_visit, nothing in the device
+build -- and runs, in a child process per scene, the photometric pass (3-level pyramid) of view 4 of the nine-view synthetic scene with pm_sweep2_kernel<4,2> forced.
+Prints, per level (image width): tap wave-loads, active lanes per load, mean blocks per wave-load under the shipped view-major order and under the pixel-major order it
+replaced (the same indices, regrouped), mean blocks per quad, and the share of quads by the number of blocks they touch.  Not a pass / fail test:
+profiles/lane_order_census.txt is its output."""
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CHILD = """
+import sys
+sys.path.insert(0, %(root)r)
+from openmvs_amd import patchmatch, synth
+from openmvs_amd.patchmatch import PatchMatchHIP, default_params
+patchmatch.load_library()
+W, H = %(w)d, %(h)d
+sc = synth.make_scene(9, W, H, n_src=8)
+e = PatchMatchHIP(0)
+e.tuning(wideMaxViews=-1, sweepLanes=4, wideHyps=-1)
+e.Init(False)
+ids = [4] + list(sc.neighbors[4])
+d, n, c = e.EstimateDepthMap(sc.gray, sc.K, sc.R, sc.C, ids, sc.dmin[4], sc.dmax[4], params=default_params(seed=5, nSubResolutionLevels=2))
+print("scene %%dx%%d, 9 views, view 4 against 8 sources, photometric pass over 3 levels: valid %%.3f" %% (W, H, float((d > 0).mean())), file=sys.stderr)
+e.close()
+"""
+
+
+def build():
+    from openmvs_amd import build as b
+    from tests import emu
+    cxx = emu._clang()
+    if cxx is None:
+        raise SystemExit("no clang++ to build the emulated library")
+    srcs, deps = b.LIBS["libpmhip.so"]
+    out = os.path.join(emu.OUT, "libpmhip_census.so")
+    srcs_abs = [os.path.join(emu.CSRC, s) for s in srcs]
+    if b._stale(out, srcs_abs + [os.path.normpath(os.path.join(emu.CSRC, d)) for d in deps] + [os.path.join(emu.EMU, "hip", "hip_runtime.h")]):
+        os.makedirs(emu.OUT, exist_ok=True)
+        subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value", "-Wno-unknown-attributes", "-DPM_GATHER_CENSUS",
+                               "-I", emu.EMU] + srcs_abs + ["-o", out + ".tmp"], cwd=emu.CSRC)
+        os.replace(out + ".tmp", out)
+    return out
+
+
+def main(argv):
+    sizes = [tuple(int(v) for v in a.lower().split("x")) for a in argv] or [(512, 288), (960, 540)]
+    lib = build()
+    env = dict(os.environ, PMHIP_LIB=lib, OPENMVS_AMD_TEST_EMULATOR="1")
+    for w, h in sizes:
+        r = subprocess.run([sys.executable, "-c", CHILD % dict(root=ROOT, w=w, h=h)], env=env, stderr=subprocess.PIPE, text=True)
+        lines = [ln for ln in r.stderr.splitlines() if ln.startswith(("scene ", "gather census:"))]
+        if r.returncode != 0 or len(lines) < 2:
+            sys.stderr.write(r.stderr)
+            raise SystemExit("the census run of %dx%d failed (exit %d)" % (w, h, r.returncode))
+        print("\n".join(lines), flush=True)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
