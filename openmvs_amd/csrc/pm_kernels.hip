@@ -471,8 +471,8 @@ __device__ __forceinline__ PMImgBuf pm_make_imgbuf(const PMTask& t) {
 // X = position of the row's first tap.  The reference returns thRobust at the first tap that leaves the image (DepthMap.cpp:484-485).  Here a tap outside
 // only raises a flag and its address is clamped, so there is no branch between taps: the 20 loads of the row are issued back to back and the sums of a flagged
 // hypothesis are simply discarded -- identical result, no load ever depends on a previous load.  This is the GUARDED path: every position is the IEEE quotient
-// whatever the operands (pm_div2).  The init kernel scores with it (one evaluation per pixel), the sweep kernels only redo a patch with it (0 of 5.9 M evaluations in
-// the emulator's census) -- as four 4-byte loads per sample also there: with 16-byte loads the redo path alone took pm_sweep2_kernel<4,2> from 127 to 136 VGPRs, i.e.
+// whatever the operands (pm_div2).  The init kernel scores with it (one evaluation per pixel), the sweep kernels only redo a patch with it (11 of 939 642 evaluations of an ordinary
+// 96x72 scene, a third of them once a source looks the other way: the census of tests/test_emu_tap_fallbacks.py) -- as four 4-byte loads per sample also there: with 16-byte loads the redo path alone took pm_sweep2_kernel<4,2> from 127 to 136 VGPRs, i.e.
 // from four waves per SIMD to three (measured 1 % on the 100-view benchmark, profiles/r05_call4_ab_100.log).
 template <bool QUAD>
 __device__ __forceinline__ void pm_tap_row_global(const pm_gcf img, int sw, int sh, float h0, float h3, float h6, float X0, float X1, float X2,
@@ -599,6 +599,16 @@ __device__ __forceinline__ void pm_taps_fast(const PMImgBuf& rs, unsigned qbase,
 	pm_row_consume<BUF, 0>(pa, qa, wts + 20, sum, sumSq, num);
 }
 
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
+// Census of pm_score_view's decisions (host build with -DPM_DEBUG_REDO only: tests/emu.py builds libpmhip_emu_redo.so with it, the device code and the shipped library
+// know nothing of it).  Row 0: the init kernel (PF = false), row 1: the sweep kernels; per row: optimistic evaluations (patches gathered through pm_taps_fast), of these
+// rechecked -- branch (4), all 25 positions again -- and redone through the guarded path -- branch (1) --, and evaluations the EARLY corner test ended before any load.
+// The fibers of the emulator run one after the other: plain counters.
+inline unsigned long long pm_tap_census[2][4];
+extern "C" __attribute__((visibility("default"))) void pm_debug_tap_census(unsigned long long out[8], int reset) {
+	for (int i = 0; i < 8; ++i) { if (out) out[i] = pm_tap_census[i / 4][i % 4]; if (reset) pm_tap_census[i / 4][i % 4] = 0; }
+}
+#endif
 // ScorePixelImage for this lane's source view, DepthMap.cpp:465-564.
 // sf0..3: the (view-independent) smoothness factors of the up-to-4 close neighbours, in insertion order; exactly 1.f for a neighbour that does not exist or does
 // not take part (DepthMap.cpp:524-533).
@@ -656,6 +666,9 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 #pragma unroll
 			for (int j = 0; j < 4; ++j) { c0 += H[0]; c1 += H[3]; c2 += H[6]; }
 			if (c2 >= 9.094947e-13f && c2 <= 1.0995116e12f) { pm_div2_inrange(c0, c1, c2, &cx, &cy); outside = outside || !pm_inside1(cx, cy, sw, sh); }
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
+			if (outside) pm_tap_census[PF][3]++;
+#endif
 			if (outside) return kp.thRobust;
 		}
 		const unsigned qbase = ((const unsigned*)(hot + 13))[0];
@@ -664,8 +677,8 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		PMTapRange rg = {0x7fffffff, (int)0x80000000, 0x7fffffff, (int)0x80000000, (int)0x80000000};
 		pm_taps_fast<MODE == 2>(rs, qbase, imgQ, sw, sh, H, bX0, bX1, bX2, wts, sum, sumSq, num, rg);
 		// (1) exact: 2^-40 <= z <= 2^40 on the whole patch (the extremes of z are among the corners, PMTapRange) and `sane` start values: every quotient of the patch was
-		//     the correctly rounded one, so the sums are pm_tap_row_global's and a tap's position is the one the reference tests.  Otherwise (0 of 38 M evaluations in the
-		//     emulator's census) the whole patch is redone through the guarded path.
+		//     the correctly rounded one, so the sums are pm_tap_row_global's and a tap's position is the one the reference tests.  Otherwise (0 - 11 of 0.3 - 0.9 M evaluations of an
+		//     ordinary 96x72 scene, 33 % with a source that looks the other way: the PM_DEBUG_REDO census, tests/test_emu_tap_fallbacks.py) the whole patch is redone through the guarded path.
 		// (2) a corner fails isInsideWithBorder<1>: the reference returns thRobust at that tap at the latest -- outside.
 		// (3) every corner inside by at least delta = 2^-17 max(w, h) and zhi <= 2 zlo: every tap is inside.  In real arithmetic on the float start values and steps the taps
 		//     T(i,j) = b + i c + j r are affine in (i, j) with z > 0, so the positions T.xy / T.z lie in the convex hull of the four corner positions.  A float tap differs
@@ -680,8 +693,7 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		const bool allIn = rg.plo >= pm_f2i(1.f + delta) && rg.pxhi <= pm_f2i((float)(sw - 2) - delta) && rg.pyhi <= pm_f2i((float)(sh - 2) - delta)
 			&& (unsigned)rg.zhi - (unsigned)rg.zlo <= 0x00800000u;   // zhi <= 2 zlo on the bit patterns of positive floats (one exponent step)
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
-		{ static unsigned long long c[3]; static bool reg = false; if (!reg) { reg = true; atexit([] { fprintf(stderr, "optimistic evaluations %llu, positions rechecked %llu, redone %llu\n", c[0], c[1], c[2]); }); }
-		  c[0]++; if (exact && cornersIn && !allIn) c[1]++; if (!exact) c[2]++; }
+		pm_tap_census[PF][0]++; if (exact && cornersIn && !allIn) pm_tap_census[PF][1]++; if (!exact) pm_tap_census[PF][2]++;
 #endif
 		if (exact) {
 			oob = !cornersIn;
@@ -1298,6 +1310,8 @@ __global__ void pm_math_kernel(int kind, const float* __restrict__ a, const floa
 		case 7: o[i] = pm_hypot_d(a[i], b[i]); break;
 		case 8: { float qx, qy; pm_div2(a[i], b[i] * 3.0f, b[i], &qx, &qy); o[i] = qx; } break;
 		case 9: { float qx, qy; pm_div2(b[i], a[i], b[i] + a[i], &qx, &qy); o[i] = qy; } break;
+		case 10: { float qx, qy; pm_div2_inrange(a[i], 1.f, b[i], &qx, &qy); o[i] = qx; } break;   // the unguarded chain, either slot of the packed pair
+		case 11: { float qx, qy; pm_div2_inrange(1.f, a[i], b[i], &qx, &qy); o[i] = qy; } break;
 		default: o[i] = a[i] / b[i]; break;
 		}
 	}

@@ -97,8 +97,18 @@ PM_HD void pm_div2(float x, float y, float z, float* qx, float* qy) {
 	*qx = x / z; *qy = y / z;
 #endif
 }
-// The fast branch of pm_div2 without its range test, for callers that establish the range themselves (the sweep kernel's tap rows check
-// 2^-40 <= z <= 2^40 and |x|, |y| < 1e18 once per row, after the fact, and redo the row through pm_div2 when that fails).
+// The fast branch of pm_div2 without its range test, for callers that establish the range themselves (pm_score_view: 2^-40 <= z <= 2^40 on the whole patch from its
+// corner taps and |x|, |y| < 5e17 from the start values, after the fact; a patch that fails is redone through pm_div2).  What the chain returns on that domain, checked
+// on the device against '/' over 3 x 2^20 operand pairs -- both ends of the z range, every power of two between them and their neighbours, numerators from the smallest
+// normal float to 5e17, quotients astride 1, w - 2 and h - 2 (tests/test_zz_gpu_tap_fallbacks.py; a host build is '/' and cannot see any of this):
+//  - numerator +0, or |x| >= 2^-102 and an exact quotient of magnitude >= 2^-126: the IEEE quotient, bit for bit.  The residual x - z q is a multiple of 2^(e - 47),
+//    2^e the leading power of two of x, and fits 24 bits: a float, the FMA returns it exactly, as long as 2^(e - 47) >= 2^-149.
+//  - numerator -0: +0 (the residual is +0 + -0 = +0, and so is the corrected quotient), where '/' gives -0.
+//  - 0 < |x| < 2^-102, or a subnormal exact quotient: the residuals underflow and the last place may be wrong (measured: 1 ulp in 758 of 2^20 log-uniform numerators,
+//    all below 2.5e-35).  The result stays next to the exact one, below 2^-61 resp. 2^-125.
+// The last two cases need no guard: such a position is below 1, as a float and as a bit pattern, whichever of the values it is -- the tap is outside the image for the
+// reference and for every test of pm_score_view alike -- and the sums of an accepted patch (all positions >= 1, so |x| >= z >= 2^-40) never hold one.  (pm_div2's fast
+// branch is the same chain and shares the two cases.)
 PM_HD void pm_div2_inrange(float x, float y, float z, float* qx, float* qy) {
 #if defined(__HIP_DEVICE_COMPILE__)
 	// the two quotients as one packed chain (v_pk_mul_f32, 4 x v_pk_fma_f32): a packed FMA issues in about the time of a plain one on this part (4.8 vs 4.2

@@ -1059,6 +1059,7 @@ void orc_math_eval(int kind, const float* a, const float* b, float* o, size_t n)
 		case 7: o[i] = pm_hypot_d(a[i], b[i]); break;
 		case 8: o[i] = a[i] / b[i]; break;                 // reference value of pm_div2's first quotient
 		case 9: o[i] = a[i] / (b[i] + a[i]); break;        // ... and of its second quotient, other operand roles
+		case 10: case 11: o[i] = a[i] / b[i]; break;       // reference value of either quotient of pm_div2_inrange
 		default: o[i] = a[i] / b[i]; break;
 		}
 	}

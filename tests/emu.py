@@ -27,11 +27,13 @@ def _clang():
     return None
 
 
-def build(name: str) -> str:
-    """Build (if stale) and return the path of an emulated library; skips the calling test when no clang++ is available."""
+def build(name: str, defines=(), out_name: str | None = None) -> str:
+    """Build (if stale) and return the path of an emulated library; skips the calling test when no clang++ is available.  `defines` (names or NAME=value, passed as -D)
+    with `out_name` build a variant beside the plain library: libpmhip_emu_redo.so = libpmhip_emu.so with PM_DEBUG_REDO, the tap path's census (pm_kernels.hip)."""
+    assert bool(defines) == bool(out_name), "a variant needs its own output name"
     srcs, deps = _build.LIBS[LIBS[name]]
     srcs_abs = [os.path.join(CSRC, s) for s in srcs]
-    out = os.path.join(OUT, name)
+    out = os.path.join(OUT, out_name or name)
     hdr = os.path.join(EMU, "hip", "hip_runtime.h")
     if not _build._stale(out, srcs_abs + [os.path.normpath(os.path.join(CSRC, d)) for d in deps] + [hdr]):
         return out
@@ -39,16 +41,16 @@ def build(name: str) -> str:
     if cxx is None:
         pytest.skip("no clang++ to build the emulated libraries")
     os.makedirs(OUT, exist_ok=True)
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value", "-Wno-unknown-attributes",
-                           "-I", EMU] + srcs_abs + ["-o", out + ".tmp"], cwd=CSRC)
+    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value", "-Wno-unknown-attributes"]
+                          + ["-D" + d for d in defines] + ["-I", EMU] + srcs_abs + ["-o", out + ".tmp"], cwd=CSRC)
     os.replace(out + ".tmp", out)
     return out
 
 
 @contextlib.contextmanager
-def emulated(module, env_var, name):
+def emulated(module, env_var, name, defines=(), out_name=None):
     """Make `module.load_library()` (openmvs_amd.patchmatch / openmvs_amd.sgm) return the emulated library inside the block."""
-    path = build(name)
+    path = build(name, defines, out_name)
     saved_lib, saved_env, saved_flag = module._LIB, os.environ.get(env_var), os.environ.get("OPENMVS_AMD_TEST_EMULATOR")
     module._LIB = None
     os.environ[env_var] = path
@@ -71,3 +73,12 @@ def counters(module):
     out = (ctypes.c_uint64 * 4)()
     module.load_library().hipemu_counters(out)
     return tuple(int(v) for v in out)
+
+
+def tap_census(module, reset=True):
+    """pm_score_view's census from a library built with PM_DEBUG_REDO (libpmhip_emu_redo.so): {"init" | "sweep": {optimistic, rechecked, redone, early_outside}}."""
+    import ctypes
+    out = (ctypes.c_ulonglong * 8)()
+    module.load_library().pm_debug_tap_census(out, 1 if reset else 0)
+    names = ("optimistic", "rechecked", "redone", "early_outside")
+    return {k: dict(zip(names, (int(v) for v in out[4 * r:4 * r + 4]))) for r, k in enumerate(("init", "sweep"))}

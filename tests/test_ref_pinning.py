@@ -124,6 +124,23 @@ def test_geometric_round_with_neighbour_depth_maps(scene):
             d, n, c = a
 
 
+@pytest.mark.parametrize("case", ["behind", "twin", "twin_shift", "edge_on"])
+def test_adversarial_cameras_of_the_tap_fallback_cases(case):
+    """The cameras of tests/tap_fallback_cases.py: a source that looks the other way (every tap has z <= 0; ScorePixelImage has no z test and samples such a tap when x / z
+    lands in the image), twins of the reference whose taps land exactly on the edge of the border band, a planted plane whose picture is the band's edge itself.  What the
+    oracle restates for them -- and the kernels' fallbacks are compared with -- is the reference's own behaviour: init pass, then init + 3 sweeps + end."""
+    from tests import tap_fallback_cases as tc
+    c = tc.inputs(case)
+    views, keep = po.make_views(c["gray"], c["K"], c["R"], c["C"], c["ids"])
+    z = np.zeros((tc.H, tc.W), np.float32)
+    d0 = z if c["depth"] is None else c["depth"]; n0 = np.zeros((tc.H, tc.W, 3), np.float32) if c["normal"] is None else c["normal"]
+    args = (views, len(c["ids"]), d0, n0, z, c["dmin"], c["dmax"], po.default_opt(seed=tc.SEED, viewID=c["ref"], rngMode=2))
+    _eq(pr.orc_run_level(*args, True, 0, 0), pr.ref_run_level(*args, True, 0, 0), "%s: init pass" % case)
+    a = pr.orc_run_level(*args, True, 0, 3, th_end=0.9 * 1.333); b = pr.ref_run_level(*args, True, 0, 3, th_end=0.9 * 1.333)
+    _eq(a, b, "%s: init + 3 sweeps + end" % case)
+    assert (a[0] > 0).mean() > 0.5
+
+
 def test_low_resolution_prior_and_mask(scene):
     sc = scene; v = 2
     opt = po.default_opt(rngMode=2)

@@ -34,20 +34,10 @@ e.close()
 
 
 def build():
-    from openmvs_amd import build as b
     from tests import emu
-    cxx = emu._clang()
-    if cxx is None:
+    if emu._clang() is None:
         raise SystemExit("no clang++ to build the emulated library")
-    srcs, deps = b.LIBS["libpmhip.so"]
-    out = os.path.join(emu.OUT, "libpmhip_census.so")
-    srcs_abs = [os.path.join(emu.CSRC, s) for s in srcs]
-    if b._stale(out, srcs_abs + [os.path.normpath(os.path.join(emu.CSRC, d)) for d in deps] + [os.path.join(emu.EMU, "hip", "hip_runtime.h")]):
-        os.makedirs(emu.OUT, exist_ok=True)
-        subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value", "-Wno-unknown-attributes", "-DPM_GATHER_CENSUS",
-                               "-I", emu.EMU] + srcs_abs + ["-o", out + ".tmp"], cwd=emu.CSRC)
-        os.replace(out + ".tmp", out)
-    return out
+    return emu.build("libpmhip_emu.so", defines=["PM_GATHER_CENSUS"], out_name="libpmhip_census.so")
 
 
 def main(argv):
