@@ -87,8 +87,12 @@ PM_HD void pmfu_normalW(const PMFuseCam& c, const float* n, float* o) {
 	o[1] = (float)(((0.0 + c.R[1] * (double)n[0]) + c.R[4] * (double)n[1]) + c.R[7] * (double)n[2]);
 	o[2] = (float)(((0.0 + c.R[2] * (double)n[0]) + c.R[5] * (double)n[1]) + c.R[8] * (double)n[2]);
 }
-PM_HD float pmfu_conf2weight(float conf, float depth) { const float a = 1.f - conf; return 1.f / ((a > 0.03f ? a : 0.03f) * depth * depth); }
-PM_HD int pmfu_round2int(float x) { return (int)pm_floorf(x + .5f); }
+// Conf2Weight (SceneDensify.cpp:120-122): MAXF is std::max, (a < b) ? b : a -- a NaN confidence stays NaN and makes the weight, and with it the point, NaN
+PM_HD float pmfu_conf2weight(float conf, float depth) { const float a = 1.f - conf; return 1.f / ((a < 0.03f ? 0.03f : a) * depth * depth); }
+// Round2Int = (int)floor(x + .5f).  The conversion of a NaN or of a value outside int is not defined by the language: the reference as built on x86 gets INT_MIN for all of
+// them (cvttss2si), the GPU's conversion saturates and turns NaN into 0 -- a pixel inside the image.  So the test comes first and both sides run the same defined code: whatever
+// is not inside int is INT_MIN, i.e. outside every image (pmfu_target) and 0 as a colour (pmfu_toU8).  Finite values inside int convert as before.
+PM_HD int pmfu_round2int(float x) { const float f = pm_floorf(x + .5f); return f >= -2147483648.f && f < 2147483648.f ? (int)f : -2147483647 - 1; }
 PM_HD uint8_t pmfu_toU8(float v) { const int i = pmfu_round2int(v); return (uint8_t)(i < 0 ? 0 : i > 255 ? 255 : i); }
 
 // the seed's 3D point (float, as stored in PointCloud::points) from pixel p of image A

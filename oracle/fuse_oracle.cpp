@@ -41,7 +41,8 @@ void projectP3(const Cam& c, const float* X, float* q) {
 void normalW(const Cam& c, const float* n, float* o) {
 	for (int i = 0; i < 3; ++i) { double s = 0; for (int k = 0; k < 3; ++k) s += c.R[k*3+i] * (double)n[k]; o[i] = (float)s; }
 }
-inline float conf2weight(float conf, float depth) { const float a = 1.f - conf; return 1.f / ((a > 0.03f ? a : 0.03f) * depth * depth); }
+// MAXF(1.f - conf, 0.03f) is std::max, (a < b) ? b : a: a NaN confidence stays NaN (pinned by tests/test_ref_fuse.py on the hostile scene)
+inline float conf2weight(float conf, float depth) { const float a = 1.f - conf; return 1.f / ((a < 0.03f ? 0.03f : a) * depth * depth); }
 inline int round2int(float x) { return (int)floorf(x + .5f); }
 inline uint8_t toU8(float v) { int i = round2int(v); return (uint8_t)(i < 0 ? 0 : i > 255 ? 255 : i); }
 }

@@ -7,11 +7,12 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <vector>
 #include "../../openmvs_amd/csrc/pm_fuse.h"
 
 extern "C" {
-struct EmuFuseView { const float* depth; const float* normal; const float* conf; const uint8_t* bgr; double K[9], R[9], C[3]; const uint32_t* neighbors; uint32_t nNeighbors; int w, h; };   // (w, h: carried by the oracle's layout; this harness runs the uniform-size case)
+struct EmuFuseView { const float* depth; const float* normal; const float* conf; const uint8_t* bgr; double K[9], R[9], C[3]; const uint32_t* neighbors; uint32_t nNeighbors; int w, h; };   // (w, h: this view's own map size, 0 = the call's; the slabs and the iw / ih arrays are laid out as the engine lays them out)
 struct EmuFuseCloud { uint64_t nPoints, nDepths, nViews; float* points; uint32_t* viewStart; uint32_t* views; float* weights; uint16_t* projs; uint8_t* colors; float* normals; };
 
 static uint64_t g_rounds = 0, g_seeds = 0;
@@ -19,7 +20,7 @@ void emu_fuse_stats(uint64_t* rounds, uint64_t* seeds) { *rounds = g_rounds; *se
 
 static void shuffle(std::vector<uint32_t>& v, uint64_t& st, int mode) {
 	if (mode == 0) return;
-	if (mode == 1) { std::reverse(v.begin(), v.end()); return; }
+	if (mode == 1) { std::sort(v.begin(), v.end(), std::greater<uint32_t>()); return; }   // (descending in both phases: reversing twice a round left the commit phase ascending)
 	for (size_t i = v.size(); i > 1; --i) { st = st * 6364136223846793005ull + 1442695040888963407ull; std::swap(v[i-1], v[(st >> 33) % i]); }
 }
 
@@ -31,7 +32,15 @@ int emu_fuse_depth_maps(const EmuFuseView* vs, int nImages, int w, int h, const 
 	const int mode = m ? atoi(m) : 2;
 	uint64_t st = 12345;
 	if ((unsigned)nImages < nMinViewsFuse) nMinViewsFuse = (unsigned)nImages;
-	const size_t P = (size_t)w * h;
+	for (int i = 0; i < nImages; ++i) if (vs[i].nNeighbors > PMFU_MAXNB) return 9;   // the engine refuses such a view (pmhip_scene_set_view: PMHIP_E_ARG); it never truncates
+	// a slab holds the largest image (ensureFuse); iw / ih are passed only when the sizes differ, as pmhip_scene_fuse does
+	std::vector<int> iw(nImages), ih(nImages);
+	size_t P = (size_t)w * h; bool slabs = false;
+	for (int i = 0; i < nImages; ++i) {
+		iw[i] = vs[i].w ? vs[i].w : w; ih[i] = vs[i].h ? vs[i].h : h;
+		P = std::max(P, (size_t)iw[i] * ih[i]); slabs = slabs || iw[i] != w || ih[i] != h;
+	}
+	auto pix = [&](int i) { return (size_t)iw[i] * ih[i]; };
 	std::vector<PMFuseCam> cams(nImages);
 	std::vector<float> depth(P * nImages, 0.f), normal, conf;
 	std::vector<uint8_t> bgr;
@@ -44,11 +53,11 @@ int emu_fuse_depth_maps(const EmuFuseView* vs, int nImages, int w, int h, const 
 	for (int i = 0; i < nImages; ++i) {
 		memcpy(cams[i].K, vs[i].K, 72); memcpy(cams[i].R, vs[i].R, 72); memcpy(cams[i].C, vs[i].C, 24); pmfu_composeP(cams[i]);
 		if (vs[i].depth) {
-			memcpy(&depth[P * i], vs[i].depth, P * 4);
-			if (bNormalMap) memcpy(&normal[P * 3 * i], vs[i].normal, P * 12);
-			if (hasConf) memcpy(&conf[P * i], vs[i].conf, P * 4);
+			memcpy(&depth[P * i], vs[i].depth, pix(i) * 4);
+			if (bNormalMap) memcpy(&normal[P * 3 * i], vs[i].normal, pix(i) * 12);
+			if (hasConf) memcpy(&conf[P * i], vs[i].conf, pix(i) * 4);
 		}
-		if (hasBgr) memcpy(&bgr[P * 3 * i], vs[i].bgr, P * 3);
+		if (hasBgr) memcpy(&bgr[P * 3 * i], vs[i].bgr, pix(i) * 3);
 	}
 	if (bEstimateNormal && !bNormalMap) bEstimateNormal = 0;
 	std::vector<uint32_t> claimed(P * nImages, PMFU_NO_ID), resv(P * nImages, PMFU_FREE);
@@ -63,6 +72,8 @@ int emu_fuse_depth_maps(const EmuFuseView* vs, int nImages, int w, int h, const 
 		if (!vs[A].depth) continue;
 		PMFuseCtx c; memset(&c, 0, sizeof(c));
 		c.w = w; c.h = h; c.nImages = nImages; c.A = A; c.nNb = 0;
+		c.slab = P; if (slabs) { c.iw = iw.data(); c.ih = ih.data(); }
+		const uint32_t PA = (uint32_t)pix(A);                 // image A's own pixels: seeds, records, compaction
 		for (uint32_t n = 0; n < vs[A].nNeighbors && c.nNb < PMFU_MAXNB; ++n) { const uint32_t b = vs[A].neighbors[n]; if ((int)b != A && vs[b].depth) c.nb[c.nNb++] = (int)b; }
 		c.depth = depth.data(); c.normal = bNormalMap ? normal.data() : nullptr; c.conf = hasConf ? conf.data() : nullptr; c.bgr = hasBgr ? bgr.data() : nullptr;
 		c.claimed = claimed.data(); c.resv = resv.data(); c.cams = cams.data();
@@ -73,11 +84,11 @@ int emu_fuse_depth_maps(const EmuFuseView* vs, int nImages, int w, int h, const 
 		std::fill(recN.begin(), recN.end(), 0);
 		std::vector<uint32_t> pending, next;
 		if (merge) {                                           // the merge kernel, threads in a shuffled order
-			std::vector<uint32_t> all(P); for (uint32_t p = 0; p < (uint32_t)P; ++p) all[p] = p;
+			std::vector<uint32_t> all(PA); for (uint32_t p = 0; p < PA; ++p) all[p] = p;
 			shuffle(all, st, mode);
 			for (uint32_t p : all) { pmfu_merge(c, p); nDepths += recN[p]; }
 		} else
-		for (uint32_t p = 0; p < (uint32_t)P; ++p) {          // the seed kernel
+		for (uint32_t p = 0; p < PA; ++p) {                   // the seed kernel
 			if (depth[P * A + p] == 0) continue;
 			++nDepths;
 			if (claimed[P * A + p] != PMFU_NO_ID) continue;
@@ -97,7 +108,7 @@ int emu_fuse_depth_maps(const EmuFuseView* vs, int nImages, int w, int h, const 
 			pending.swap(next);
 		}
 		for (size_t i = 0; i < resv.size(); ++i) if (resv[i] != PMFU_FREE) return 8;   // every reservation must have been released
-		for (uint32_t p = 0; p < (uint32_t)P; ++p) {           // compaction (scan + scatter kernels)
+		for (uint32_t p = 0; p < PA; ++p) {                    // compaction (scan + scatter kernels)
 			const int nv = recN[p];
 			if (!nv) continue;
 			oStart.push_back((uint32_t)oViews.size());

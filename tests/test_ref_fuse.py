@@ -9,6 +9,7 @@ from openmvs_amd import synth
 from oracle import pyoracle as po
 from oracle import pyref as pr
 from tests import fuse_cases as fc
+from tests import fuse_contention_cases as cc
 
 pytestmark = pytest.mark.skipif(not pr.fuse_available(), reason="oracle/_ref/libref_fuse.so not built (needs /root/reference)")
 
@@ -83,6 +84,25 @@ def test_fuse_of_depth_maps_of_different_sizes_is_the_reference_function(seed, o
         ref = dict(ref); orc = dict(orc); ref["weights"] = None; orc["weights"] = None
     _same(ref, orc, "mixed sizes %s" % opts)
     assert ref["nPoints"] > 1000
+
+
+CONTENTION = cc.all_cases((cc.SMALL,)) | {"hostile@%dx%d" % s: cc.hostile(*s) for s in cc.THIN} | {"eighteen": cc.eighteen(*cc.SMALL)}
+
+
+@pytest.mark.parametrize("name", sorted(CONTENTION))
+def test_contended_and_hostile_scenes_fuse_as_in_the_reference(name):
+    """The scenes of tests/fuse_contention_cases.py: funnels, order-dependent outcomes, 17 and 18 views per point, thresholds straddled by one ulp, maps of different sizes, and
+    depths, confidences and normals that are not numbers (the reference as built here converts NaN and out-of-range values to INT_MIN: outside every image, 0 as a colour).  The
+    reference sorts the images itself; the oracle is given that order, as above.  Bits are compared, those of the NaNs included."""
+    c = CONTENTION[name]
+    ref, order = pr.ref_fuse_depth_maps(c.deps, c.nrms, c.cnfs, c.bgrs, c.K, c.R, c.C, c.nbs(), **c.kw)
+    orc = c.fuse(order=order)
+    if ref["nPoints"] == 0:                                # (of an empty cloud the reference's harness returns no colour and normal arrays at all)
+        assert orc["nPoints"] == 0 and name.split("@")[0] in ("compaction_empty", "funnel_occluded", "tie_depth_out", "tie_normal_out")
+        return
+    _same(ref, orc, name)
+    if order == c.order and c.check:
+        c.check(c, ref | {"projs": orc["projs"], "nDepths": orc["nDepths"]})          # (the reference keeps the projections and the count of depths in locals)
 
 
 # ---- MVS::EstimateNormalMap (DepthMap.cpp:1522-1613, verbatim) against openmvs_amd.views.estimate_normal_map ---------------------------------------------------
