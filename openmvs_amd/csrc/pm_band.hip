@@ -15,9 +15,6 @@
 #ifndef PM_BAND_MINWAVES_PHOTO
 #define PM_BAND_MINWAVES_PHOTO 4   // the photometric instantiations fit four waves per SIMD (128 VGPRs) without scratch
 #endif
-#ifndef PM_BAND_MINWAVES_PHOTO
-#define PM_BAND_MINWAVES_PHOTO 4   // the photometric instantiations fit four waves per SIMD (128 VGPRs) without scratch
-#endif
 
 // Per-pixel state of a visit, in LDS.  The G lanes of a pixel (PPW lanes apart) all need it and all hold the same values, so one lane writes and all read: what lives in
 // registers while a hypothesis is scored (the long part of a visit) is then only what the scoring itself needs -- the register budget that decides how
@@ -137,7 +134,7 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 	}
 	__syncthreads();
 	PM_TICK(12); PM_COUNT(9, 1);
-	// ---- ProcessPixel's control flow as a per-pixel state machine: every outer trip scores at most one hypothesis per pixel (as pm_sweep_kernel) ----
+	// ---- ProcessPixel's control flow as a per-pixel state machine: every outer trip scores at most one hypothesis per pixel ----
 	enum { ST_PROP0 = 0, ST_PROP1 = 1, ST_DECIDE = 2, ST_RAND = 3, ST_REFINE = 4, ST_DONE = 5 };
 	const uint32_t k1 = t.k1base + pass;
 	for (;;) {
@@ -305,7 +302,7 @@ __global__ __launch_bounds__(64, (GEO ? PM_BAND_MINWAVES : PM_BAND_MINWAVES_PHOT
 	__shared__ float2 s_w[PPW][PM_NT + 1];
 	__shared__ double s_src[NV * NBD];
 	__shared__ PMPix s_pix[PPW];
-	// XCD-aware block mapping as in pm_sweep_kernel: contiguous (view, chunk) ranges per XCD
+	// XCD-aware block mapping: contiguous (view, chunk) ranges per XCD
 	unsigned vbx = blockIdx.x, vby = blockIdx.y;
 	{
 		const unsigned nbx = gridDim.x, nwg = nbx * gridDim.y, orig = blockIdx.y * nbx + blockIdx.x;

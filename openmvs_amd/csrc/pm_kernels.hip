@@ -925,7 +925,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_init_kernel(const PMTask* __restr
 }
 
 // -------------------------------------------------------------------------------------------
-// ProcessPixel in "latency mode": ONE WAVE PER PIXEL.  pm_sweep_kernel gives a wave 64 / G pixels and walks each pixel's hypotheses one after the
+// ProcessPixel in "latency mode": ONE WAVE PER PIXEL.  pm_sweep2_kernel gives a wave 64 / G pixels and walks each pixel's hypotheses one after the
 // other (<= 2 propagation candidates, then <= nRandomIters refinements or random restarts); with one depth map (BASELINE config 2) or a handful of
 // them a diagonal launch cannot fill 1 024 SIMDs and its duration is one wave's serial chain of ~8 evaluations.  Here the eight 8-lane groups of the
 // wave belong to the same pixel and each scores a DIFFERENT hypothesis in the same round (lane = candidate * 8 + source view):
@@ -954,7 +954,7 @@ __global__ __launch_bounds__(64, PM_WIDE_MINWAVES) void pm_sweep_wide_kernel(con
 	const size_t idx = (size_t)y * w + x;
 	const pm_gf gDepth = pm_globw(t.depth), gNormal = pm_globw(t.normal), gConf = pm_globw(t.conf);
 	const int sgn = dir == 0 ? -1 : 1;
-	// neighbour slots as in pm_sweep_kernel: slot0 (x+sgn,y), slot1 (x,y+sgn) are the propagation sources, slot2 (x-sgn,y), slot3 (x,y-sgn)
+	// neighbour slots as in pm_step_pixel: slot0 (x+sgn,y), slot1 (x,y+sgn) are the propagation sources, slot2 (x-sgn,y), slot3 (x,y-sgn)
 	size_t qis[4]; bool bok[4]; int qxs[4], qys[4];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {

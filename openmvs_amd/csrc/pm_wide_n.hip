@@ -12,8 +12,9 @@
 // the regular kernel; profiles/r03_small_batches_call24_26_narrower_speculation.log).  Measured: the two-wide kernel is the fastest of all mappings from 4 to at
 // least 25 views (13 views: 23.6 Mpix/s against 17.9 with one view per lane and 17.5 eight-wide; 25 views: 32.5 against 28.2), the engine's default there.
 //
-// (NH = 8 of this template would be pm_sweep_wide_kernel without its LDS-window option; folding the two is left for the round that next touches pm_kernels.hip, whose
-// text is tied to the committed counter measurement of this round.)
+// (NH = 8 of this template would be pm_sweep_wide_kernel.  The fold was built and measured and is not taken: every other kernel kept its machine code and the maps their
+// bits, but a 1080p depth map went from 0.720 to 0.731 s at best, 0.765 s with this body as it stands -- profiles/fold_eight_wide_ab.log.  The two bodies stay apart;
+// a fix to one's hypotheses, draws or accept rule belongs in both.)
 // Differences from pm_sweep_wide_kernel, all forced by several pixels sharing a wave: a pixel that is masked / done does not leave (its lanes idle to the end of
 // the wave's loop); every cross-lane read (the other groups' scores and planes) is done by all lanes before the per-pixel replay, never inside its
 // data-dependent control flow; window-less tap rows only (the quad images).
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(64, PM_WIDEN_MINWAVES) void pm_sweep_widen_kernel(c
 	const pm_gf gDepth = pm_globw(t.depth), gNormal = pm_globw(t.normal), gConf = pm_globw(t.conf);
 	const pm_gcf oDepthM = pm_glob(t.depthOld), oNormalM = pm_glob(t.normalOld), oConfM = pm_glob(t.confOld);   // tiled sweeps: neighbours in another tile (PMStep)
 	const int sgn = st.dir == 0 ? -1 : 1;
-	// neighbour slots as in pm_sweep_kernel: slot0 (x+sgn,y), slot1 (x,y+sgn) are the propagation sources, slot2 (x-sgn,y), slot3 (x,y-sgn)
+	// neighbour slots as in pm_step_pixel: slot0 (x+sgn,y), slot1 (x,y+sgn) are the propagation sources, slot2 (x-sgn,y), slot3 (x,y-sgn)
 	size_t qis[4]; bool bok[4]; int qxs[4], qys[4];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
