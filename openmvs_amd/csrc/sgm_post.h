@@ -15,6 +15,12 @@
 #define SGMP_INVALID ((uint8_t)0)
 #define SGMP_HW 3                           // halfWindowSizeX/Y
 
+// float -> int where the language leaves the conversion undefined: the reference as built on x86 gets INT_MIN (cvttss2si's "integer indefinite") for a NaN and
+// for everything outside int, the GPU saturates and turns a NaN into 0.  Test first, convert second (as pmfu_round2int, pm_fuse.h); finite values inside int
+// keep the plain truncation.  oracle/sgm_post_oracle.cpp includes this header for these two functions, so both sides convert alike.
+PM_HD int sgmp_f2i(float v) { return v >= -2147483648.f && v < 2147483648.f ? (int)v : -2147483647 - 1; }
+PM_HD int sgmp_addw(int a, int b) { return (int)((unsigned)a + (unsigned)b); }   // a + b of values that may be INT_MIN: wraps like the x86 add, never overflows
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SGMP_ATOMIC_MAX(p, v) atomicMax((p), (v))
 #else
@@ -115,7 +121,7 @@ PM_HD int16_t sgmp_refine(int16_t d, int minDisp, int maxDisp, const uint16_t* a
 	if (d == minDisp) disparity += sgmp_semisubpixel(accums[i], accums[i + 1]);
 	else if (d + 1 == maxDisp) disparity -= sgmp_semisubpixel(accums[i], accums[i - 1]);
 	else disparity += sgmp_subpixel(accums[i - 1], accums[i], accums[i + 1], mode);
-	return (int16_t)(int)pm_floorf(disparity * (float)steps + .5f);
+	return (int16_t)sgmp_f2i(pm_floorf(disparity * (float)steps + .5f));
 }
 
 // ---- Disparity2RangeMap (:1350-1444): per low-resolution pixel, the disparity search range for the next tSGM level from the median / minimum /
@@ -183,7 +189,7 @@ PM_HD int sgmp_clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 // bilinear sample of the valid neighbours only; valid(v): float maps v > 0, int16 maps v != NO_DISP.  T = float or int16_t / uint16_t
 template <typename T, typename VALID>
 PM_HD bool sgmp_sample_safe(const T* img, int w, int h, float px, float py, VALID valid, float* out) {
-	const int lx = (int)px, ly = (int)py;
+	const int lx = sgmp_f2i(px), ly = sgmp_f2i(py);      // (at most 2^31 - 128: lx + 1 cannot overflow)
 	const float x = px - (float)lx, x1 = 1.f - x, y = py - (float)ly, y1 = 1.f - y;
 	const T v00 = img[(size_t)sgmp_clampi(ly, h) * w + sgmp_clampi(lx, w)], v10 = img[(size_t)sgmp_clampi(ly, h) * w + sgmp_clampi(lx + 1, w)];
 	const T v01 = img[(size_t)sgmp_clampi(ly + 1, h) * w + sgmp_clampi(lx, w)], v11 = img[(size_t)sgmp_clampi(ly + 1, h) * w + sgmp_clampi(lx + 1, w)];
@@ -225,7 +231,7 @@ PM_HD int16_t sgmp_depth2disparity_px(const float* depth, int dw, int dh, const 
 	float u[2]; sgmp_project_h(invH, c + SGMP_HW, r + SGMP_HW, u);
 	float dep, disp;
 	if (!sgmp_sample_safe(depth, dw, dh, u[0], u[1], SgmpValidDepth(), &dep) || !sgmp_depth2disparity(invQ, u[0], u[1], dep, &disp)) return SGMP_NO_DISP;
-	return (int16_t)(int)pm_floorf(disp * (float)steps + .5f);
+	return (int16_t)sgmp_f2i(pm_floorf(disp * (float)steps + .5f));
 }
 // Disparity2DepthMap, one pixel (r,c) of the depth map; cost may be null
 PM_HD void sgmp_disparity2depth_px(const int16_t* disp, const uint16_t* cost, int w, int h, const double* H, const double* Q, int steps, int r, int c, float* depth, float* conf) {
@@ -280,12 +286,12 @@ PM_HD bool sgmp_proj_source(const int16_t* disp, const uint16_t* cost, int w, co
 	float ux = 0.f, uy = 0.f;
 	const float depth = sgmp_disparity2depth_pt(Q, dx, dy, disparity, &ux, &uy);
 	if (depth <= 0) return false;
-	const int center = (int16_t)(int)pm_floorf(disparity);
+	const int center = (int16_t)sgmp_f2i(pm_floorf(disparity));
 	o->depth = depth;
 	o->rangeX = sgmp_disparity2depth_i(Q, dx, dy, (float)(center - 1));
 	o->rangeY = sgmp_disparity2depth_i(Q, dx, dy, (float)(center + 1));
 	o->conf = cost ? 1.f / (float)((int)cost[(size_t)r * w + c] + 1) : 0.f;
-	o->x = (int)pm_floorf(ux); o->y = (int)pm_floorf(uy);
+	o->x = sgmp_f2i(pm_floorf(ux)); o->y = sgmp_f2i(pm_floorf(uy));
 	o->ux = ux - 0.5f; o->uy = uy - 0.5f;
 	return true;
 }
@@ -294,7 +300,7 @@ PM_HD void sgmp_proj_splat(const int16_t* disp, const uint16_t* cost, int w, con
 	if (!sgmp_proj_source(disp, cost, w, Q, steps, r, c, &s)) return;
 	const unsigned long long src = (unsigned long long)((size_t)r * w + c);
 	for (int i = -1; i <= 1; ++i) for (int j = -1; j <= 1; ++j) {
-		const int nx = s.x + j, ny = s.y + i;
+		const int nx = sgmp_addw(s.x, j), ny = sgmp_addw(s.y, i);
 		if (nx < 0 || ny < 0 || nx >= dw || ny >= dh) continue;
 		const float ddx = (float)nx - s.ux, ddy = (float)ny - s.uy;
 		if (pm_fabsf(ddx) > 0.75f || pm_fabsf(ddy) > 0.75f) continue;

@@ -9,6 +9,7 @@
 #include <string.h>
 #include <vector>
 #include "../openmvs_amd/csrc/pm_math.h"
+#include "../openmvs_amd/csrc/sgm_post.h"   // sgmp_f2i / sgmp_addw only: the float -> int conversions the language leaves undefined, defined as x86 performs them
 
 namespace {
 const int16_t NO_DISP = 32767;
@@ -93,7 +94,7 @@ void orc_sgm_refine(int16_t* disp, const OrcSgmPixel* pixels, const uint16_t* ac
 		if (d == pixel.minDisp) disparity += Fit::semisubpixel(acc[idxDisp], acc[idxDisp + 1]);
 		else if (d + 1 == pixel.maxDisp) disparity -= Fit::semisubpixel(acc[idxDisp], acc[idxDisp - 1]);
 		else disparity += Fit::subpixelMode(acc[idxDisp - 1], acc[idxDisp], acc[idxDisp + 1], mode);
-		d = (int16_t)(int)floorf(disparity * steps + .5f);
+		d = (int16_t)sgmp_f2i(floorf(disparity * steps + .5f));
 	}
 }
 } // extern "C"
@@ -112,7 +113,7 @@ int getMedian(std::vector<int16_t>& v) {   // cList::GetMedian<Disparity>, libs/
 }
 template <typename T> T getPixel(const T* img, int w, int h, int y, int x) { x = x < 0 ? 0 : (x >= w ? w - 1 : x); y = y < 0 ? 0 : (y >= h ? h - 1 : y); return img[(size_t)y * w + x]; }
 template <typename T, typename F> bool sampleSafe(const T* img, int w, int h, float px, float py, F functor, float& v) {   // Types.inl:2315-2332
-	const int lx = (int)px, ly = (int)py;
+	const int lx = sgmp_f2i(px), ly = sgmp_f2i(py);
 	const float x = px - lx, x1 = 1.f - x, y = py - ly, y1 = 1.f - y;
 	const T x0y0 = getPixel(img, w, h, ly, lx), x1y0 = getPixel(img, w, h, ly, lx + 1), x0y1 = getPixel(img, w, h, ly + 1, lx), x1y1 = getPixel(img, w, h, ly + 1, lx + 1);
 	const bool b00 = functor(x0y0), b10 = functor(x1y0), b01 = functor(x0y1), b11 = functor(x1y1);
@@ -201,7 +202,7 @@ void orc_sgm_depth2disparity_map(const float* depthMap, int dw, int dh, const do
 			if (fabs(ww) < 1e-7) ok = false;
 			else { const double z = (invQ[8] * u[0] + invQ[9] * u[1] + invQ[10]) * depth + invQ[11]; disparity = -(float)(z / ww); }
 		}
-		disparityMap[(size_t)r * w + c] = ok ? (int16_t)(int)floorf(disparity * subpixelSteps + .5f) : NO_DISP;
+		disparityMap[(size_t)r * w + c] = ok ? (int16_t)sgmp_f2i(floorf(disparity * subpixelSteps + .5f)) : NO_DISP;
 	}
 }
 void orc_sgm_disparity2depth_map(const int16_t* disparityMap, const uint16_t* costMap, int w, int h, const double* H, const double* Q, int subpixelSteps,
@@ -260,13 +261,13 @@ int orc_sgm_project_disparity2depth_map(const int16_t* disparityMap, const uint1
 		const int dx[2] = {c + HW, r + HW};
 		const float depth = disparity2depthPt(Q, dx[0], dx[1], disparity, u);
 		if (depth <= 0) continue;
-		const int16_t disparityCenter = (int16_t)(int)floorf(disparity);
+		const int16_t disparityCenter = (int16_t)sgmp_f2i(floorf(disparity));
 		const float rangeX = disparity2depth(Q, dx[0], dx[1], (float)(disparityCenter - 1)), rangeY = disparity2depth(Q, dx[0], dx[1], (float)(disparityCenter + 1));
 		const float cost = costMap ? 1.f / (costMap[(size_t)r * w + c] + 1) : 0.f;
-		const int x[2] = {(int)floorf(u[0]), (int)floorf(u[1])};
+		const int x[2] = {sgmp_f2i(floorf(u[0])), sgmp_f2i(floorf(u[1]))};
 		u[0] -= 0.5f; u[1] -= 0.5f;
 		for (int i = -1; i <= 1; ++i) for (int j = -1; j <= 1; ++j) {
-			const int nx[2] = {x[0] + j, x[1] + i};
+			const int nx[2] = {sgmp_addw(x[0], j), sgmp_addw(x[1], i)};
 			if (!(nx[0] >= 0 && nx[1] >= 0 && nx[0] < dw && nx[1] < dh)) continue;
 			const float dist[2] = {(float)nx[0] - u[0], (float)nx[1] - u[1]};
 			if (fabsf(dist[0]) > overlapBorder || fabsf(dist[1]) > overlapBorder) continue;

@@ -9,14 +9,17 @@
 #include "../../openmvs_amd/csrc/sgm_post.h"
 
 namespace {
+int g_order = 0;          // emu_sgm_set_order: 0 = scrambled (the default), 1 = ascending, 2 = descending, other values = scrambled with another seed
 std::vector<size_t> order(size_t n, uint64_t seed) {
-	std::vector<size_t> v(n); for (size_t i = 0; i < n; ++i) v[i] = i;
-	uint64_t st = seed * 2654435761u + 12345;
+	std::vector<size_t> v(n); for (size_t i = 0; i < n; ++i) v[i] = g_order == 2 ? n - 1 - i : i;
+	if (g_order == 1 || g_order == 2) return v;
+	uint64_t st = (seed + 1000u * (uint64_t)g_order) * 2654435761u + 12345;
 	for (size_t i = n; i > 1; --i) { st = st * 6364136223846793005ull + 1442695040888963407ull; std::swap(v[i-1], v[(st >> 33) % i]); }
 	return v;
 }
 }
 extern "C" {
+void emu_sgm_set_order(int mode) { g_order = mode; }
 struct EmuSgmPixel { unsigned long long idx; short minDisp, maxDisp; int pad; };
 void emu_sgm_cross_check(int16_t* l2r, const int16_t* r2l, int wl, int h, int wr, int thCross) {
 	for (size_t i : order((size_t)wl * h, 1)) sgmp_cross_check(l2r, r2l, wl, wr, (int)(i / wl), (int)(i % wl), thCross);

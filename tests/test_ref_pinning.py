@@ -541,3 +541,33 @@ def test_sgm_pair_fusion_is_the_reference_loop(w, h, seed, n_pairs):
         assert np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), "Fuse confidence, minViews %d" % mv
         any_valid += int((a[0] > 0).sum())
     assert any_valid > 0
+
+
+# ---- the same steps on the hand-built maps of tests/sgm_post_edge_cases.py: the oracle equals the reference's own functions where contention, ties, int16 wraps and the
+#      float -> int conversions decide.  The reference is built for x86, whose conversion gives INT_MIN for NaN and for everything outside int: that is what sgmp_f2i
+#      (csrc/sgm_post.h, shared by the oracle) defines, so the hostile coordinates and disparities are pinned too.  Not compared: what the reference leaves unset (range and
+#      confidence of ProjectDisparity2DepthMap where it produced no depth); NaN results by position only.  The speckle filter is OpenCV's: no reference function here. ----
+def _edge_params():
+    from tests import sgm_post_edge_cases as ec
+    return [(f, s) for f in sorted(ec.FAMILIES) if f != "speckles" for s in (ec.SMALL,) + ec.THIN]
+
+
+@sgm_only
+@pytest.mark.parametrize("family,size", _edge_params(), ids=lambda v: "%dx%d" % v if isinstance(v, tuple) else v)
+def test_sgm_steps_on_hand_built_maps_are_the_reference_functions(family, size):
+    from tests import sgm_post_edge_cases as ec
+    assert ec.check_family(ec.Steps(pr.sgm_post_lib(), "ref_sgm_"), family, size, pin=True) > 0
+
+
+@sgm_only
+def test_sgm_refine_on_hand_built_sums_is_the_reference_function():
+    from tests import sgm_post_edge_cases as ec
+    px, acc, maps = ec.refine_synthetic()
+    bgr, gray, px2, n, mxd, mn, mx, maps2 = ec.refine_problem(*ec.SMALL)
+    acc2 = po.sgm_match(bgr, gray, gray, px2, n, mxd, 3, po.sgm_generate_p2s())[3]
+    for table, sums, dmaps in ((px, acc, maps), (px2, acc2, maps2)):
+        for name, d in dmaps.items():
+            for mode in range(7):
+                for steps in (1, 4, 64):
+                    a = po.sgm_refine(d, table, sums, mode=mode, steps=steps); b = pr.ref_sgm_refine(d, table, sums, mode=mode, steps=steps)
+                    assert np.array_equal(a, b), "RefineDisparityMap %s mode %d steps %d: %d of %d differ" % (name, mode, steps, int((a != b).sum()), a.size)
