@@ -353,6 +353,20 @@ int pmhip_math_eval(pmhip_engine* e, int kind, const float* a, const float* b, f
 int pmhip_prof_get(pmhip_engine* e, unsigned long long out16[16], int reset);
 /* Device resampling kernels on host buffers: kind 0 area (factor f = arg), 1 linear x2, 2 nearest x2. */
 int pmhip_resize(pmhip_engine* e, int kind, const float* src, int w, int h, int arg, float* dst);
+/* Any resampler of csrc/pm_kernels.hip, launched once through the helper the estimation launches it with (same grid, same block cap), on host buffers and at any
+ * size: sw x sh -> dw x dh.  dst is uploaded before the launch and read back whole, so entries the kernel does not write keep the caller's bytes.  Row-major,
+ * float unless said otherwise; P = w * h of the side in question.
+ *   AREA          src nImg images -> dst nImg images; arg = integer factor f, dw x dh = cvRound(sw / f) x cvRound(sh / f)
+ *   UPSAMPLE      src = depth[P] normal[3P] -> dst = depth[P] normal[3P] prior[P]; arg != 0: the depth is taken INTER_NEAREST too (nearestDepth)
+ *   NEAREST_DOWN  src = depth[P] normal[3P] -> dst = depth[P] normal[3P]; arg = f, sizes as for AREA
+ *   NEAREST_UP    one image, INTER_NEAREST
+ *   MASK_LEVEL    one 8-bit image, INTER_NEAREST
+ *   SKEW          nImg images -> the folded anti-diagonal-major copy, same size
+ *   QUAD          nImg images -> nImg quad images of (w + h - 1) * h float4 entries, same size
+ * nImg = 1 except where it is named.  PMHIP_E_SIZE for sizes the kind does not take. */
+enum { PMHIP_RESAMPLE_AREA = 0, PMHIP_RESAMPLE_UPSAMPLE = 1, PMHIP_RESAMPLE_NEAREST_DOWN = 2, PMHIP_RESAMPLE_NEAREST_UP = 3, PMHIP_RESAMPLE_MASK_LEVEL = 4,
+       PMHIP_RESAMPLE_SKEW = 5, PMHIP_RESAMPLE_QUAD = 6 };
+int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, void* dst, int dw, int dh, int arg, int nImg);
 
 #ifdef __cplusplus
 }

@@ -768,20 +768,66 @@ int pmhip_resize(pmhip_engine* e, int kind, const float* src, int w, int h, int 
 	DevBuf<float> ds, dd, dn, dn2, dp; DevBuf<PMUpTask> du;
 	HIPCHK(e, ds.alloc(ns)); HIPCHK(e, dd.alloc(nd));
 	HIPCHK(e, hipMemcpy(ds, src, ns * 4, hipMemcpyHostToDevice));
-	const int blocks = (int)std::min<size_t>((nd + 255) / 256, 4096);
 	if (kind == 0) {
-		hipLaunchKernelGGL(pm_area_kernel, dim3(blocks), dim3(256), 0, e->stream, ds, dd, w, h, dw, dh, arg, 1);
+		launchArea(e->stream, ds, dd, w, h, dw, dh, arg, 1);
 	} else if (kind == 1) {
 		HIPCHK(e, dn.alloc(ns * 3)); HIPCHK(e, dn2.alloc(nd * 3)); HIPCHK(e, dp.alloc(nd)); HIPCHK(e, du.alloc(1));
 		HIPCHK(e, hipMemset(dn, 0, ns * 12));
 		PMUpTask u{ds, dn, dd, dn2, dp};
 		HIPCHK(e, hipMemcpy(du, &u, sizeof(u), hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(pm_upsample_kernel, dim3(blocks, 1), dim3(256), 0, e->stream, du, w, h, dw, dh, 0);
+		launchUpsample(e->stream, du, 1, w, h, dw, dh, 0);
 	} else {
-		hipLaunchKernelGGL(pm_nearest_up_f_kernel, dim3(blocks), dim3(256), 0, e->stream, ds, dd, w, h, dw, dh);
+		launchNearestUpF(e->stream, ds, dd, w, h, dw, dh);
 	}
+	HIPCHK(e, hipGetLastError());
 	HIPCHK(e, hipStreamSynchronize(e->stream));
 	HIPCHK(e, hipMemcpy(dst, dd, nd * 4, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+// One resampler once, on host buffers, through the launch helper the estimation uses (pm_host_estimate.hip).  The destination is uploaded before the launch and
+// read back whole, so whatever the caller put into the entries a kernel does not write (a quad image's unused corners) comes back untouched -- or not.
+int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, void* dst, int dw, int dh, int arg, int nImg) {
+	if (!e || !src || !dst) return PMHIP_E_ARG;
+	if (kind < PMHIP_RESAMPLE_AREA || kind > PMHIP_RESAMPLE_QUAD) { e->err = "pmhip_resample: unknown kind"; return PMHIP_E_ARG; }
+	if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || nImg < 1) { e->err = "pmhip_resample: empty image"; return PMHIP_E_SIZE; }
+	const bool factor = kind == PMHIP_RESAMPLE_AREA || kind == PMHIP_RESAMPLE_NEAREST_DOWN, same = kind == PMHIP_RESAMPLE_SKEW || kind == PMHIP_RESAMPLE_QUAD;
+	if (factor && (arg < 1 || dw != (int)nearbyint((double)sw / arg) || dh != (int)nearbyint((double)sh / arg))) { e->err = "pmhip_resample: the destination is not cvRound(size / factor)"; return PMHIP_E_SIZE; }
+	if (same && (dw != sw || dh != sh)) { e->err = "pmhip_resample: skew and quad keep the size"; return PMHIP_E_SIZE; }
+	if (nImg != 1 && !(kind == PMHIP_RESAMPLE_AREA || same)) { e->err = "pmhip_resample: one image for this kind"; return PMHIP_E_ARG; }
+	HIPCHK(e, hipSetDevice(e->device));
+	const size_t ps = (size_t)sw * sh, pd = (size_t)dw * dh;
+	// bytes of the two buffers, by kind (include/pmhip.h)
+	size_t bs = ps * 4 * nImg, bd = pd * 4 * nImg;
+	switch (kind) {
+	case PMHIP_RESAMPLE_UPSAMPLE: bs = ps * 16; bd = pd * 20; break;
+	case PMHIP_RESAMPLE_NEAREST_DOWN: bs = ps * 16; bd = pd * 16; break;
+	case PMHIP_RESAMPLE_MASK_LEVEL: bs = ps; bd = pd; break;
+	case PMHIP_RESAMPLE_QUAD: bd = (size_t)(dw + dh - 1) * dh * 16 * nImg; break;
+	default: break;
+	}
+	DevBuf<unsigned char> ds, dd; DevBuf<PMUpTask> du;
+	HIPCHK(e, ds.alloc(bs)); HIPCHK(e, dd.alloc(bd));
+	HIPCHK(e, hipMemcpy(ds, src, bs, hipMemcpyHostToDevice));
+	HIPCHK(e, hipMemcpy(dd, dst, bd, hipMemcpyHostToDevice));
+	const float* fs = (const float*)(const unsigned char*)ds; float* fd = (float*)(unsigned char*)dd;
+	switch (kind) {
+	case PMHIP_RESAMPLE_AREA: launchArea(e->stream, fs, fd, sw, sh, dw, dh, arg, nImg); break;
+	case PMHIP_RESAMPLE_UPSAMPLE: case PMHIP_RESAMPLE_NEAREST_DOWN: {
+		PMUpTask u{fs, fs + ps, fd, fd + pd, kind == PMHIP_RESAMPLE_UPSAMPLE ? fd + pd * 4 : nullptr};
+		HIPCHK(e, du.alloc(1));
+		HIPCHK(e, hipMemcpy(du, &u, sizeof(u), hipMemcpyHostToDevice));
+		if (kind == PMHIP_RESAMPLE_UPSAMPLE) launchUpsample(e->stream, du, 1, sw, sh, dw, dh, arg ? 1 : 0);
+		else launchNearestDown(e->stream, du, 1, sw, sh, dw, dh, arg);
+	} break;
+	case PMHIP_RESAMPLE_NEAREST_UP: launchNearestUpF(e->stream, fs, fd, sw, sh, dw, dh); break;
+	case PMHIP_RESAMPLE_MASK_LEVEL: launchMaskLevel(e->stream, ds, dd, sw, sh, dw, dh); break;
+	case PMHIP_RESAMPLE_SKEW: launchSkew(e->stream, fs, fd, sw, sh, nImg); break;
+	default: launchQuad(e->stream, fs, (float4*)fd, sw, sh, nImg); break;
+	}
+	HIPCHK(e, hipGetLastError());
+	HIPCHK(e, hipStreamSynchronize(e->stream));
+	HIPCHK(e, hipMemcpy(dst, dd, bd, hipMemcpyDeviceToHost));
 	return 0;
 }
 

@@ -30,19 +30,40 @@ static int ensureOld(pmhip_engine* e) {
 	return 0;
 }
 
+// The launches of the resamplers (pm_kernels.hip, "resampling"), one helper each: the pyramid and the level hand-off below and the self-test hook pmhip_resample
+// (pm_engine.hip) launch through these, so the hook runs production's grid, block cap included.  n outputs in blocks of 256, at most `cap` blocks; the kernels stride.
+static inline unsigned resampleBlocks(size_t n, size_t cap) { return (unsigned)std::min<size_t>((n + 255) / 256, cap); }
+static void launchArea(hipStream_t st, const float* src, float* dst, int sw, int sh, int dw, int dh, int f, int nImg) {
+	hipLaunchKernelGGL(pm_area_kernel, dim3(resampleBlocks((size_t)dw * dh * nImg, 65535)), dim3(256), 0, st, src, dst, sw, sh, dw, dh, f, nImg);
+}
+static void launchSkew(hipStream_t st, const float* src, float* dst, int w, int h, int nImg) {
+	hipLaunchKernelGGL(pm_skew_kernel, dim3(resampleBlocks((size_t)w * h * nImg, 65535)), dim3(256), 0, st, src, dst, w, h, nImg);
+}
+static void launchQuad(hipStream_t st, const float* src, float4* dst, int w, int h, int nImg) {
+	hipLaunchKernelGGL(pm_quad_kernel, dim3(resampleBlocks((size_t)w * h * nImg, 65535)), dim3(256), 0, st, src, dst, w, h, nImg);
+}
+static void launchMaskLevel(hipStream_t st, const unsigned char* src, unsigned char* dst, int sw, int sh, int dw, int dh) {
+	hipLaunchKernelGGL(pm_mask_level_kernel, dim3(resampleBlocks((size_t)dw * dh, 4096)), dim3(256), 0, st, src, dst, sw, sh, dw, dh);
+}
+// the level hand-off of nT views (ups[0 .. nT), device memory)
+static void launchNearestDown(hipStream_t st, const PMUpTask* ups, int nT, int sw, int sh, int dw, int dh, int f) {
+	hipLaunchKernelGGL(pm_nearest_down_kernel, dim3(resampleBlocks((size_t)dw * dh, 4096), nT), dim3(256), 0, st, ups, sw, sh, dw, dh, f);
+}
+static void launchUpsample(hipStream_t st, const PMUpTask* ups, int nT, int sw, int sh, int dw, int dh, int nearestDepth) {
+	hipLaunchKernelGGL(pm_upsample_kernel, dim3(resampleBlocks((size_t)dw * dh, 4096), nT), dim3(256), 0, st, ups, sw, sh, dw, dh, nearestDepth);
+}
+// (no call site in the estimation: the self-test hooks only)
+static void launchNearestUpF(hipStream_t st, const float* src, float* dst, int sw, int sh, int dw, int dh) {
+	hipLaunchKernelGGL(pm_nearest_up_f_kernel, dim3(resampleBlocks((size_t)dw * dh, 4096)), dim3(256), 0, st, src, dst, sw, sh, dw, dh);
+}
+
 static int buildPyramid(pmhip_engine* e) {
 	if (!e->pyramidDirty) return 0;
-	for (int l = 1; l <= e->nLevels; ++l) {
-		const size_t n = (size_t)e->lw(l) * e->lh(l) * e->nImages;
-		const int blocks = (int)std::min<size_t>((n + 255) / 256, 65535);
-		// every level is resampled from the full-resolution image (ScaleDepthData(fullRes, 1/2^l), SceneDensify.cpp:654)
-		hipLaunchKernelGGL(pm_area_kernel, dim3(blocks), dim3(256), 0, e->stream, e->d_img[0], e->d_img[l], e->w, e->h, e->lw(l), e->lh(l), 1 << l, e->nImages);
-	}
+	// every level is resampled from the full-resolution image (ScaleDepthData(fullRes, 1/2^l), SceneDensify.cpp:654)
+	for (int l = 1; l <= e->nLevels; ++l) launchArea(e->stream, e->d_img[0], e->d_img[l], e->w, e->h, e->lw(l), e->lh(l), 1 << l, e->nImages);
 	for (int l = 0; l <= e->nLevels; ++l) {
-		const size_t n = (size_t)e->lw(l) * e->lh(l) * e->nImages;
-		const int blocks = (int)std::min<size_t>((n + 255) / 256, 65535);
-		hipLaunchKernelGGL(pm_skew_kernel, dim3(blocks), dim3(256), 0, e->stream, e->d_img[l], e->d_imgS[l], e->lw(l), e->lh(l), e->nImages);
-		hipLaunchKernelGGL(pm_quad_kernel, dim3(blocks), dim3(256), 0, e->stream, e->d_img[l], e->d_imgQ[l], e->lw(l), e->lh(l), e->nImages);
+		launchSkew(e->stream, e->d_img[l], e->d_imgS[l], e->lw(l), e->lh(l), e->nImages);
+		launchQuad(e->stream, e->d_img[l], e->d_imgQ[l], e->lw(l), e->lh(l), e->nImages);
 	}
 	HIPCHK(e, hipGetLastError());
 	e->pyramidDirty = false;
@@ -55,15 +76,13 @@ static int buildSidePyramids(pmhip_engine* e) {
 		for (int l = 1; l <= e->nLevels; ++l) {
 			const int lw = lvlSize(v.sw, l), lh = lvlSize(v.sh, l);
 			if (lw < 1 || lh < 1 || !v.sImg[l]) break;      // a view too small for this level has no pyramid entry there (estimateBatch reports PMHIP_E_SIZE if the level is used)
-			const size_t n = (size_t)lw * lh;
-			hipLaunchKernelGGL(pm_area_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, e->stream, v.sImg[0], v.sImg[l], v.sw, v.sh, lw, lh, 1 << l, 1);
+			launchArea(e->stream, v.sImg[0], v.sImg[l], v.sw, v.sh, lw, lh, 1 << l, 1);
 		}
 		for (int l = 0; l <= e->nLevels; ++l) {
 			const int lw = lvlSize(v.sw, l), lh = lvlSize(v.sh, l);
 			if (lw < 1 || lh < 1 || !v.sImg[l]) break;
-			const size_t n = (size_t)lw * lh;
-			hipLaunchKernelGGL(pm_skew_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, e->stream, v.sImg[l], v.sImgS[l], lw, lh, 1);
-			hipLaunchKernelGGL(pm_quad_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, e->stream, v.sImg[l], v.sImgQ[l], lw, lh, 1);
+			launchSkew(e->stream, v.sImg[l], v.sImgS[l], lw, lh, 1);
+			launchQuad(e->stream, v.sImg[l], v.sImgQ[l], lw, lh, 1);
 		}
 		HIPCHK(e, hipGetLastError());
 		v.sideDirty = false;
@@ -212,10 +231,9 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 				if (mv.sw) {   // a view with its own size: its own level masks
 					const int mlw = lvlSize(mv.sw, l), mlh = lvlSize(mv.sh, l);
 					if (mlw < 1 || mlh < 1 || !mv.oMask[l]) continue;
-					hipLaunchKernelGGL(pm_mask_level_kernel, dim3((unsigned)std::min<size_t>(((size_t)mlw * mlh + 255) / 256, 4096)), dim3(256), 0, e->stream, mv.oMask[0], mv.oMask[l], mv.sw, mv.sh, mlw, mlh);
+					launchMaskLevel(e->stream, mv.oMask[0], mv.oMask[l], mv.sw, mv.sh, mlw, mlh);
 				} else
-					hipLaunchKernelGGL(pm_mask_level_kernel, dim3((unsigned)std::min<size_t>((Pm + 255) / 256, 4096)), dim3(256), 0, e->stream,
-						e->d_mask[0] + (size_t)e->w * e->h * i, e->d_mask[l] + Pm * i, e->w, e->h, e->lw(l), e->lh(l));
+					launchMaskLevel(e->stream, e->d_mask[0] + (size_t)e->w * e->h * i, e->d_mask[l] + Pm * i, e->w, e->h, e->lw(l), e->lh(l));
 			}
 		}
 		HIPCHK(e, hipGetLastError());
@@ -395,9 +413,8 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 		if (sp.kind != 2 && evOpen[g]) { evEndOn(e, evSweep[g], st); evOpen[g] = false; }
 		switch (sp.kind) {
 		case 0: {
-			const int eb = (int)std::min<size_t>((Pl + 255) / 256, 4096);
-			if (l == S) hipLaunchKernelGGL(pm_nearest_down_kernel, dim3(eb, nT), dim3(256), 0, st, du, cw, ch, lw, lh, 1 << S);
-			else hipLaunchKernelGGL(pm_upsample_kernel, dim3(eb, nT), dim3(256), 0, st, du, lvlSize(cw, l + 1), lvlSize(ch, l + 1), lw, lh, nearestDepth);
+			if (l == S) launchNearestDown(st, du, nT, cw, ch, lw, lh, 1 << S);
+			else launchUpsample(st, du, nT, lvlSize(cw, l + 1), lvlSize(ch, l + 1), lw, lh, nearestDepth);
 			return true;
 		}
 		case 1: {

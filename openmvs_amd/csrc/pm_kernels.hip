@@ -1231,7 +1231,7 @@ __global__ void pm_quad_kernel(const float* __restrict__ src, float4* __restrict
 	}
 }
 __device__ __forceinline__ void pm_linear_coef(int d, int dn, int sn, int& s, float& a) {
-	const double scale = (double)sn / (double)dn;
+	const double scale = pm_resize_scale(dn, sn);
 	float f = (float)(((double)d + 0.5) * scale - 0.5);
 	int si = (int)pm_floorf(f);
 	f -= (float)si;
@@ -1254,8 +1254,7 @@ __global__ void pm_upsample_kernel(const PMUpTask* __restrict__ ups, int sw, int
 		const float t0 = u.sdepth[(size_t)y0 * sw + x0] * a0 + u.sdepth[(size_t)y0 * sw + x1] * a1;
 		const float t1 = u.sdepth[(size_t)y1 * sw + x0] * a0 + u.sdepth[(size_t)y1 * sw + x1] * a1;
 		float dv = t0 * b0 + t1 * b1;
-		const int nx = min((int)floor((double)x * ((double)sw / (double)dw)), sw - 1);
-		const int ny = min((int)floor((double)y * ((double)sh / (double)dh)), sh - 1);
+		const int nx = pm_nn_index(x, dw, sw), ny = pm_nn_index(y, dh, sh);
 		const size_t si = (size_t)ny * sw + nx;
 		if (nearestDepth) dv = u.sdepth[si];
 		u.ddepth[i] = dv; u.dprior[i] = dv;
@@ -1279,8 +1278,7 @@ __global__ void pm_nearest_up_f_kernel(const float* __restrict__ s, float* __res
 	const size_t n = (size_t)dw * dh;
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
 		const int x = (int)(i % dw), y = (int)(i / dw);
-		const int nx = min((int)floor((double)x * ((double)sw / (double)dw)), sw - 1);
-		const int ny = min((int)floor((double)y * ((double)sh / (double)dh)), sh - 1);
+		const int nx = pm_nn_index(x, dw, sw), ny = pm_nn_index(y, dh, sh);
 		d[i] = s[(size_t)ny * sw + nx];
 	}
 }
@@ -1290,8 +1288,7 @@ __global__ void pm_mask_level_kernel(const unsigned char* __restrict__ s, unsign
 	const size_t n = (size_t)dw * dh;
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
 		const int x = (int)(i % dw), y = (int)(i / dw);
-		const int nx = min((int)floor((double)x * ((double)sw / (double)dw)), sw - 1);
-		const int ny = min((int)floor((double)y * ((double)sh / (double)dh)), sh - 1);
+		const int nx = pm_nn_index(x, dw, sw), ny = pm_nn_index(y, dh, sh);
 		d[i] = s[(size_t)ny * sw + nx];
 	}
 }

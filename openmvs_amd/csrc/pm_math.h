@@ -157,6 +157,16 @@ PM_HD float pm_floorf(float x) {
 	return floorf(x);
 #endif
 }
+// cv::resize(..., dsize, INTER_NEAREST): the source index of destination index d along an axis of sn source and dn destination pixels.  OpenCV's order of
+// operations, in double: inv_scale = dn / sn (resize), ifx = 1. / inv_scale (resizeNN), sx = min(cvFloor(d * ifx), sn - 1).  NOT d * (sn / dn): the two
+// roundings fall on opposite sides of an integer d * sn / dn for some sizes (58 -> 14 at d = 7: 28 here, 29 there).  Every nearest resize of the project
+// goes through this one rule (the kernels of pm_kernels.hip, the oracle; views.import_ignore_mask and tsgm.resize_nearest_u8 restate it in numpy).
+PM_HD int pm_nn_index(int d, int dn, int sn) {
+	const int s = (int)__builtin_floor((double)d * (1.0 / ((double)dn / (double)sn)));
+	return s < sn - 1 ? s : sn - 1;
+}
+// the source-per-destination scale of cv::resize(..., dsize, INTER_LINEAR) along such an axis, by the same order of operations (scale_x = 1. / inv_scale_x)
+PM_HD double pm_resize_scale(int dn, int sn) { return 1.0 / ((double)dn / (double)sn); }
 PM_HD float pm_fabsf(float x) { return pm_u2f(pm_f2u(x) & 0x7fffffffu); }
 // bit pattern of a float as a signed integer: for non-negative floats the integer order is the float order, every negative float (and -0) is below every
 // non-negative one and a NaN with a clear sign bit is above every number -- which is all a "is every value inside [lo, hi], lo >= 0" test needs, on the integer

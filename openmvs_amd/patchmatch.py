@@ -77,7 +77,7 @@ EXPORTS = ["pmhip_working_size", "pmhip_scaled_size", "pmhip_image_prepare", "pm
            "pmhip_estimate_depth_map", "pmhip_estimate_depth_map_masked", "pmhip_last_error", "pmhip_scene_create", "pmhip_scene_set_view",
            "pmhip_scene_estimate", "pmhip_scene_commit_round", "pmhip_scene_reset_view", "pmhip_scene_set_maps",
            "pmhip_scene_get_maps", "pmhip_scene_device_ptr", "pmhip_scene_copy", "pmhip_scene_filter", "pmhip_scene_filter_commit", "pmhip_scene_gap_interpolation", "pmhip_scene_remove_small_segments", "pmhip_scene_images_updated", "pmhip_scene_maps_updated", "pmhip_scene_bytes", "pmhip_sync",
-           "pmhip_stream", "pmhip_stats_reset", "pmhip_stats_get", "pmhip_prof_get", "pmhip_math_eval", "pmhip_resize", "pmhip_set_sweep_tiles", "pmhip_abi_version"]
+           "pmhip_stream", "pmhip_stats_reset", "pmhip_stats_get", "pmhip_prof_get", "pmhip_math_eval", "pmhip_resize", "pmhip_resample", "pmhip_set_sweep_tiles", "pmhip_abi_version"]
 
 _LIB = None
 
@@ -102,7 +102,7 @@ def load_library() -> C.CDLL:
             lib.pmhip_image_bytes.restype = C.c_uint64
         experiment = bool(os.environ.get("PMHIP_LIB"))        # (an older build of the library in an A/B run may lack the newest entry points)
         for n in EXPORTS:
-            if not (experiment and (n in ("pmhip_set_sweep_tiles", "pmhip_abi_version", "pmhip_working_size", "pmhip_scaled_size", "pmhip_scene_set_view_stored") or n.startswith("pmhip_image_"))):
+            if not (experiment and (n in ("pmhip_resample", "pmhip_set_sweep_tiles", "pmhip_abi_version", "pmhip_working_size", "pmhip_scaled_size", "pmhip_scene_set_view_stored") or n.startswith("pmhip_image_"))):
                 getattr(lib, n)  # raises AttributeError if a declared symbol is missing
         if hasattr(lib, "pmhip_abi_version"):
             lib.pmhip_abi_version.restype = C.c_uint32
@@ -608,6 +608,27 @@ class PatchMatchHIP:
         o = np.zeros((int(np.rint(h / arg)), int(np.rint(w / arg))) if kind == 0 else (h * 2, w * 2), np.float32)
         self._chk(self._lib.pmhip_resize(self._h, kind, _fp(img), w, h, arg, _fp(o)))
         return o
+
+    RESAMPLE_AREA, RESAMPLE_UPSAMPLE, RESAMPLE_NEAREST_DOWN, RESAMPLE_NEAREST_UP, RESAMPLE_MASK_LEVEL, RESAMPLE_SKEW, RESAMPLE_QUAD = range(7)
+
+    def resample(self, kind, src, src_size, dst, dst_size, arg=0, n_img=1):
+        """pmhip_resample: one resampler of csrc/pm_kernels.hip through production's launch, `src_size` = (sw, sh) -> `dst_size` = (dw, dh).  `src` and `dst` are flat
+        C-contiguous buffers laid out as include/pmhip.h says for the kind (uint8 for the mask level, float32 otherwise); `dst` is uploaded first and written in place, so
+        what the kernel leaves alone keeps the caller's fill.  Returns `dst`."""
+        u8 = kind == self.RESAMPLE_MASK_LEVEL
+        dt = np.uint8 if u8 else np.float32
+        (sw, sh), (dw, dh) = src_size, dst_size
+        ps, pd = sw * sh, dw * dh
+        ns, nd = {self.RESAMPLE_UPSAMPLE: (4 * ps, 5 * pd), self.RESAMPLE_NEAREST_DOWN: (4 * ps, 4 * pd),
+                  self.RESAMPLE_QUAD: (ps * n_img, (dw + dh - 1) * dh * 4 * n_img)}.get(kind, (ps * n_img, pd * n_img))
+        if not (isinstance(dst, np.ndarray) and dst.dtype == dt and dst.flags.c_contiguous and dst.flags.writeable and dst.size == nd):
+            raise ValueError("resample: dst must be a writable C-contiguous %s array of %d elements" % (np.dtype(dt).name, nd))
+        src = np.ascontiguousarray(src, dt)
+        if src.size != ns:
+            raise ValueError("resample: src must hold %d elements" % ns)
+        self._chk(self._lib.pmhip_resample(self._h, C.c_int(int(kind)), src.ctypes.data_as(C.c_void_p), C.c_int(sw), C.c_int(sh), dst.ctypes.data_as(C.c_void_p),
+                                           C.c_int(dw), C.c_int(dh), C.c_int(int(arg)), C.c_int(int(n_img))))
+        return dst
 
     def close(self):
         if getattr(self, "_h", None):

@@ -45,10 +45,10 @@ def resize_area_u8(img: np.ndarray, f: int) -> np.ndarray:
 
 
 def resize_nearest_u8(img: np.ndarray, w: int, h: int) -> np.ndarray:
-    """cv::resize(mask, size, INTER_NEAREST)."""
+    """cv::resize(mask, size, INTER_NEAREST): sx = min(floor(dx * ifx), sw - 1) with ifx = 1 / (dw / sw) in double (resizeNN; csrc/pm_math.h pm_nn_index)."""
     H, W = img.shape
-    ys = np.minimum(np.floor(np.arange(h) * (H / h)).astype(np.int64), H - 1)
-    xs = np.minimum(np.floor(np.arange(w) * (W / w)).astype(np.int64), W - 1)
+    ys = np.minimum(np.floor(np.arange(h) * (1.0 / (h / float(H)))).astype(np.int64), H - 1)
+    xs = np.minimum(np.floor(np.arange(w) * (1.0 / (w / float(W)))).astype(np.int64), W - 1)
     return img[ys][:, xs]
 
 

@@ -135,24 +135,22 @@ static void resizeNearestDownN(const ImgN& s, int f, ImgN& o) {
 	for (int y = 0; y < o.h; ++y) { const int sy = std::min(y * f, s.h - 1);
 		for (int x = 0; x < o.w; ++x) { const float* p = s.at(sy, std::min(x * f, s.w - 1)); float* q = o.at(y,x); q[0]=p[0]; q[1]=p[1]; q[2]=p[2]; } }
 }
-// INTER_NEAREST: sx = min(floor(dx*ssize/dsize), ssize-1)
+// INTER_NEAREST: sx = min(floor(dx * (1 / (dsize / ssize))), ssize-1), pm_nn_index (pm_math.h)
 static void resizeNearest(const ImgF& s, int nw, int nh, ImgF& o) {
 	o.create(nw, nh);
-	const double ifx = (double)s.w / nw, ify = (double)s.h / nh;
-	for (int y = 0; y < nh; ++y) { const int sy = std::min((int)floor(y * ify), s.h - 1);
-		for (int x = 0; x < nw; ++x) { const int sx = std::min((int)floor(x * ifx), s.w - 1); o(y,x) = s(sy,sx); } }
+	for (int y = 0; y < nh; ++y) { const int sy = pm_nn_index(y, nh, s.h);
+		for (int x = 0; x < nw; ++x) { const int sx = pm_nn_index(x, nw, s.w); o(y,x) = s(sy,sx); } }
 }
 static void resizeNearestN(const ImgN& s, int nw, int nh, ImgN& o) {
 	o.create(nw, nh);
-	const double ifx = (double)s.w / nw, ify = (double)s.h / nh;
-	for (int y = 0; y < nh; ++y) { const int sy = std::min((int)floor(y * ify), s.h - 1);
-		for (int x = 0; x < nw; ++x) { const int sx = std::min((int)floor(x * ifx), s.w - 1);
+	for (int y = 0; y < nh; ++y) { const int sy = pm_nn_index(y, nh, s.h);
+		for (int x = 0; x < nw; ++x) { const int sx = pm_nn_index(x, nw, s.w);
 			const float* p = s.at(sy,sx); float* q = o.at(y,x); q[0]=p[0]; q[1]=p[1]; q[2]=p[2]; } }
 }
 // INTER_LINEAR (float): half-pixel centres, edge clamp, horizontal pass then vertical
 static void linearCoef(int dn, int sn, std::vector<int>& idx, std::vector<float>& a) {
 	idx.resize(dn); a.resize(dn);
-	const double scale = (double)sn / dn;
+	const double scale = pm_resize_scale(dn, sn);   // 1 / (dn / sn), cv::resize's order
 	for (int d = 0; d < dn; ++d) {
 		float f = (float)((d + 0.5) * scale - 0.5);
 		int s = (int)floorf(f);
@@ -788,9 +786,8 @@ static int EstimateDepthMap(DepthData& full, const Opt& opt, int nGeometricIter,
 		std::vector<unsigned char> levelMask;
 		if (ignoreMask) {   // cv::resize(mask, size, INTER_NEAREST), then DepthData::ApplyIgnoreMask (DepthMap.cpp:215-231)
 			levelMask.resize((size_t)w * h);
-			const double ifx = (double)W0 / w, ify = (double)H0 / h;
-			for (int y = 0; y < h; ++y) { const int sy = std::min((int)floor(y * ify), H0 - 1);
-				for (int x = 0; x < w; ++x) { const int sx = std::min((int)floor(x * ifx), W0 - 1); levelMask[(size_t)y * w + x] = ignoreMask[(size_t)sy * W0 + sx]; } }
+			for (int y = 0; y < h; ++y) { const int sy = pm_nn_index(y, h, H0);
+				for (int x = 0; x < w; ++x) { const int sx = pm_nn_index(x, w, W0); levelMask[(size_t)y * w + x] = ignoreMask[(size_t)sy * W0 + sx]; } }
 			for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) if (!levelMask[(size_t)y * w + x]) {
 				dd.depthMap(y, x) = 0; float* n = dd.normalMap.at(y, x); n[0] = n[1] = n[2] = 0; dd.confMap(y, x) = 0;
 			}
