@@ -44,7 +44,13 @@ int sgmhip_generate_p2s(uint16_t P2, float alpha, float beta, uint16_t out256[25
 int sgmhip_set_problem(sgmhip_engine* e, const uint8_t* leftBGR, const float* leftGray, const float* rightGray,
                        int w, int h, const SGMHipPixelData* pixels, uint64_t numCosts, int maxNumDisp);
 /* SemiGlobalMatcher::Match(ViewData,ViewData,...): cost volume + 8-path aggregation + WTA on the
- * resident problem.  Asynchronous unless sync != 0.  P1 / P2s as in the SemiGlobalMatcher ctor. */
+ * resident problem.  Asynchronous unless sync != 0.  P1 / P2s as in the SemiGlobalMatcher ctor.
+ * Penalties that would be computed wrong are refused with SGMHIP_E_ARG (text in sgmhip_last_error), here and
+ * in sgmhip_tsgm_match / sgmhip_tsgm_match_rectified, before anything is launched:
+ *   - P1 above any entry of P2s (the recurrence is evaluated in its O(D) form, exact only for P1 <= P2);
+ *   - an entry of P2s with 8 * (255 + P2) > 65535, i.e. above 7936 (the sum of eight paths is 16 bits wide).
+ * The grey images may hold any float: the penalty of a step is P2s[min(|round(255 * dI)|, 255)], P2s[255] for a
+ * grey difference dI that is not finite, and a WZNCC score that is not finite costs 255. */
 int sgmhip_match(sgmhip_engine* e, uint16_t P1, const uint16_t P2s[256], int sync);
 /* Download results (any pointer may be NULL): disparity i16 and cost u16 per valid-grid pixel;
  * the raw cost volume (u8) and the 8-path sums (u16), numCosts entries each. */

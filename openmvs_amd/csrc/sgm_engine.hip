@@ -118,8 +118,16 @@ int sgmhip_set_problem(sgmhip_engine* e, const uint8_t* leftBGR, const float* le
 	return 0;
 }
 
-// the penalty table of the next Match on the device, and its maximum (which decides between byte deltas and u16 atomic sums)
-static int sgmSetP2s(sgmhip_engine* e, const uint16_t P2s[256]) {
+// the penalty table of the next Match on the device, and its maximum (which decides between byte deltas and u16 atomic sums).  Penalties that Match would get
+// silently wrong are refused here, for sgmhip_match and both resident tSGM entry points alike (nothing has been changed or launched when this returns an error):
+//  * P1 above an entry of P2s: the kernels evaluate the recurrence in its O(D) form, min(Lp(d), Lp(d+-1) + P1, min Lp + P2), which equals the reference's loop over all
+//    previous disparities only when P1 <= P2 (oracle/sgm_oracle.cpp: orc_sgm_step_forms_agree);
+//  * an entry with 8 * (255 + P2) > 65535, i.e. above 7936: a path's L is at most 255 + P2, the sum of the eight paths is the reference's u16 and, on the device, half of
+//    a 32-bit word that two neighbouring sums share in one atomic add without carry.
+static int sgmSetP2s(sgmhip_engine* e, uint16_t P1, const uint16_t P2s[256]) {
+	const int minP2 = *std::min_element(P2s, P2s + 256), maxP2 = *std::max_element(P2s, P2s + 256);
+	if ((int)P1 > minP2) { e->err = "P1 = " + std::to_string((int)P1) + " exceeds the smallest entry of P2s (" + std::to_string(minP2) + "): Match needs P1 <= P2"; return SGMHIP_E_ARG; }
+	if (!SGMP_SUM_FITS_U16(maxP2)) { e->err = "an entry of P2s is " + std::to_string(maxP2) + ": Match needs 8 * (255 + P2) <= 65535, the sum of eight paths in 16 bits"; return SGMHIP_E_ARG; }
 	SGMCHK(e, hipMemcpyAsync(e->d_P2s, P2s, 512, hipMemcpyHostToDevice, e->stream));
 	e->maxP2 = *std::max_element(P2s, P2s + 256);
 	return 0;
@@ -240,7 +248,7 @@ static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
 int sgmhip_match(sgmhip_engine* e, uint16_t P1, const uint16_t P2s[256], int sync) {
 	if (!e || !P2s || e->numCosts == 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
-	{ const int rc = sgmSetP2s(e, P2s); if (rc) return rc; }
+	{ const int rc = sgmSetP2s(e, P1, P2s); if (rc) return rc; }
 	{ const int rc = sgmMatch(e, P1); if (rc) return rc; }
 	if (sync) SGMCHK(e, hipStreamSynchronize(e->stream));
 	return 0;
@@ -578,7 +586,7 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 	SGMCHK(e, keys.alloc(nValid)); SGMCHK(e, ranges.alloc(nValid)); SGMCHK(e, par.alloc(nValid)); SGMCHK(e, siz.alloc(nValid));
 	const int maxTiles = (int)((nValid + SGMT_TILE - 1) / SGMT_TILE);
 	SGMCHK(e, tiles.alloc((size_t)maxTiles)); SGMCHK(e, scal.alloc(2));     // scal: {numCosts, maxNumDisp} of a level's range table
-	{ const int rc = sgmSetP2s(e, P2s); if (rc) return rc; }
+	{ const int rc = sgmSetP2s(e, P1, P2s); if (rc) return rc; }
 
 	int16_t *leftDisp = lD, *rightDisp = rD, *leftNew = lDn, *rightNew = rDn;
 	uint8_t *lm = lM, *rm = rM, *lmNext = lM2, *rmNext = rM2;

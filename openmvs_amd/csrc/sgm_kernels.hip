@@ -12,10 +12,11 @@
 // walks it in chunks of SGM_T pixels: the PixelData, cost bytes and running sums of a whole chunk
 // are requested up front (independent loads, latency overlapped), then the chunk is consumed
 // serially.  The O(D^2) inner loop of the reference (:1030-1044) is evaluated in its O(D) form
-// (valid because P1 <= P2; see oracle/sgm_oracle.cpp: orc_sgm_step_forms_agree).
+// (valid because P1 <= P2, which sgmSetP2s enforces; see oracle/sgm_oracle.cpp: orc_sgm_step_forms_agree).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pm_math.h"
+#include "sgm_post.h"   // sgmp_p2_index, sgmp_cost_of_ncc: defined once for the kernels and the oracle
 
 struct SGMPixel { unsigned long long idx; short minDisp, maxDisp; int pad; }; // == SGMHipPixelData
 // a pointer rebuilt from an integer is "generic" to the compiler (flat_load, two counters); these say it is HBM (global_load, scalar base + lane offset)
@@ -32,8 +33,6 @@ typedef const unsigned short* sgm_gcs;
 #define SGM_T 8          // pixels per prefetch chunk
 #endif
 #define SGM_INF 0x3fffffff
-
-__device__ __forceinline__ int sgm_round2int(float x) { return (int)pm_floorf(x + .5f); } // ROUND2INT, Types.h:949-955
 
 // ---- cost volume, SemiGlobalMatcher.cpp:874-985 --------------------------------------------------------------------------
 // The kernels are fp32-VALU bound (49 taps x 3 running sums per cost, all in the reference's summation order), so the design goal
@@ -65,7 +64,7 @@ __device__ __forceinline__ unsigned char sgm_cost_of(float sum, float sumSq, flo
 	const float eps = 1e-3f;
 	const float normSq1 = sumSq - (sum * sum) / sumW;
 	const float ncc = nom / pm_sqrtf(normSq0 * normSq1 + eps);
-	return ncc <= 0 ? (unsigned char)255 : (unsigned char)sgm_round2int((1.f - pm_minf(ncc, 1.f)) * 255.f);
+	return sgmp_cost_of_ncc(ncc);
 }
 
 // ---- one valid-grid pixel per LANE ----------------------------------------------------------------------------------------------------------------
@@ -360,7 +359,7 @@ __device__ __forceinline__ int sgm_sub_min16(int v) {
 }
 
 // accums(d) += L(d) (:1020,1043).  The eight path kernels run concurrently on eight streams, so the sum is an atomic add;
-// two u16 sums share a 32-bit word (no carry between halves: a sum never exceeds 8*(255+60) = 2520).  The lane whose entry sits
+// two u16 sums share a 32-bit word (no carry between halves: a sum never exceeds 8 * (255 + max P2) <= 65535, which sgmSetP2s enforces).  The lane whose entry sits
 // in the low half adds its right neighbour's value in the same atomic; an entry in a high half whose low-half partner is not in
 // this wave-instruction (lane 0) adds alone.  One predicated atomic per lane, no divergent control flow.  Called by all 64 lanes.
 __device__ __forceinline__ void sgm_accumulate(unsigned* wordsBase, unsigned par, int k, int nD, int L, int lane) {
@@ -405,8 +404,7 @@ __device__ __forceinline__ void sgm_step(int* sL, const unsigned short* sP2, con
 	const int rsMin = px.minDisp, rsMax = px.maxDisp, nD = rsMax - rsMin;
 	if (nD <= 0) return;                                            // invalid pixels do not reset Lp / Ip (:1071-1072)
 	const float DI = g - st.Ip;
-	int ip = sgm_round2int(255.f * DI); ip = ip < 0 ? -ip : ip;
-	const int P2 = sP2[ip];
+	const int P2 = sP2[sgmp_p2_index(DI)];
 	const int lo = max(st.rpMin, rsMin), hi = min(st.rpMax, rsMax);
 	const int* Lp = sL + st.cur * SL + MD + (rsMin - st.rpMin);     // Lp[k] = previous L at the disparity of entry k
 	int* Ls = sL + (st.cur ^ 1) * SL + MD;
@@ -704,8 +702,7 @@ __global__ __launch_bounds__(64) void sgm_path_uniform_kernel(const float* __res
 	for (int i0 = 0; i0 < n; i0 += 64) {
 		// the 64 penalties of this chunk: lane t has pixel i0 + t, its predecessor's grey value comes from lane t-1 (lane 0: the chunk before)
 		const float Ip = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, carry), __builtin_bit_cast(int, g), 0x138, 0xf, 0xf, false));
-		int ip = sgm_round2int(255.f * (g - Ip)); ip = ip < 0 ? -ip : ip;
-		const int P2v = (int)s_P2[ip > 255 ? 255 : ip];
+		const int P2v = (int)s_P2[sgmp_p2_index(g - Ip)];
 		carry = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g), 63));
 		g = gNext; gNext = grayLoad(i0 + 128);
 #pragma unroll 1

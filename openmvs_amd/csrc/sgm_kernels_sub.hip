@@ -129,8 +129,7 @@ __global__ __launch_bounds__(64) void sgm_path_sub_kernel(const float* __restric
 			if (!__any(on)) continue;
 			const float g = s_g[sub][slot][t];
 			const float DI = g - Ip;
-			int ip = sgm_round2int(255.f * DI); ip = ip < 0 ? -ip : ip;
-			const int P2 = s_P2[on ? ip : 0];
+			const int P2 = s_P2[on ? sgmp_p2_index(DI) : 0];
 			const int lo = max(rpMin, rsMin), hi = min(rpMax, rsMax);
 			const bool fresh = lo >= hi;                              // no common disparity (also the first pixel of a line)
 			const int off = rsMin - rpMin, nDp = rpMax - rpMin;       // Lp(d) of entry k sits at k + off if that is inside [0, nDp)

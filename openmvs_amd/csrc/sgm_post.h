@@ -21,6 +21,24 @@
 PM_HD int sgmp_f2i(float v) { return v >= -2147483648.f && v < 2147483648.f ? (int)v : -2147483647 - 1; }
 PM_HD int sgmp_addw(int a, int b) { return (int)((unsigned)a + (unsigned)b); }   // a + b of values that may be INT_MIN: wraps like the x86 add, never overflows
 
+// Match's lookup into the 256 penalties of GenerateP2s for a grey difference DI (pixelAccum, :1004): min(|ROUND2INT(255 DI)|, 255), and 255 for a DI that is
+// not finite.  The reference indexes the table with |ROUND2INT(255 DI)| as it comes, which is inside the table only for grey values in [0, 1]; the C ABI takes the
+// caller's floats, so the lookup is defined for all of them, once, for the three path kernels and oracle/sgm_oracle.cpp.  Test first, convert second: every
+// 255 DI outside (-256, 256) rounds to 256 or more in magnitude (or is no number), inside it the conversion is the plain one.
+PM_HD int sgmp_p2_index(float DI) {
+	const float x = 255.f * DI;
+	if (!(x > -256.f && x < 256.f)) return 255;
+	const int i = (int)pm_floorf(x + .5f), a = i < 0 ? -i : i;
+	return a > 255 ? 255 : a;
+}
+// the cost of a WZNCC score (:975-978): 255 for ncc <= 0 and for an ncc that is not finite (a NaN or infinite grey value in either window), else ROUND2INT((1 - min(ncc, 1)) 255)
+PM_HD uint8_t sgmp_cost_of_ncc(float ncc) {
+	return ncc > 0.f && ncc <= 3.402823466e+38f ? (uint8_t)(int)pm_floorf((1.f - pm_minf(ncc, 1.f)) * 255.f + .5f) : (uint8_t)255;
+}
+// the penalties Match computes exactly: P1 <= every entry of P2s (the O(D) form of the recurrence equals the reference's loop only then) and 8 (255 + P2) <= 65535 for
+// every entry (the sum of eight paths fits the reference's u16, and the half of a 32-bit word it shares with its neighbour on the device)
+#define SGMP_SUM_FITS_U16(P2) (8 * (255 + (int)(P2)) <= 65535)
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SGMP_ATOMIC_MAX(p, v) atomicMax((p), (v))
 #else

@@ -37,7 +37,7 @@ class OrcOpt(C.Structure):
 def build(force: bool = False) -> str:
     so = os.path.join(_HERE, "libpm_oracle.so")
     srcs = [os.path.join(_HERE, f) for f in ("pm_oracle.cpp", "sgm_oracle.cpp", "filter_oracle.cpp", "fuse_oracle.cpp", "sgm_post_oracle.cpp")] + \
-           [os.path.join(_HERE, "..", "openmvs_amd", "csrc", "pm_math.h")]
+           [os.path.join(_HERE, "..", "openmvs_amd", "csrc", h) for h in ("pm_math.h", "sgm_post.h")]
     stale = force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs if os.path.exists(s))
     if stale and all(os.path.exists(s) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-B", "libpm_oracle.so"], stdout=subprocess.DEVNULL)

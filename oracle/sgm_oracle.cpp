@@ -8,6 +8,7 @@
 // recurrence is transcribed literally, O(D^2) inner loop included (:1030-1044); the GPU uses the
 // O(D) form, so the tests also check the two forms agree.  exp() is pm_expf (shared with the GPU).
 #include "../openmvs_amd/csrc/pm_math.h"
+#include "../openmvs_amd/csrc/sgm_post.h"   // sgmp_p2_index / sgmp_cost_of_ncc only: the penalty lookup and the cost of a score, defined for every float
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -28,7 +29,7 @@ struct LineData { std::vector<AccumCost> L; Range R; };
 
 // pixelAccum lambda, SemiGlobalMatcher.cpp:1003-1046 (literal)
 static void pixelAccum(const Cost* costs, const LineData& Lp, LineData& Ls, AccumCost* accums, float DI, AccumCost P1, const AccumCost* P2s) {
-	const AccumCost P2 = P2s[std::abs(Round2Int(255.f * DI))];
+	const AccumCost P2 = P2s[sgmp_p2_index(DI)];   // the reference: P2s[abs(ROUND2INT(255.f*DI))], the same for grey values in [0, 1]
 	const Disparity minDisp = std::max(Lp.R.minDisp, Ls.R.minDisp);
 	const Disparity maxDisp = std::min(Lp.R.maxDisp, Ls.R.maxDisp);
 	if (minDisp >= maxDisp) {
@@ -108,7 +109,7 @@ static void computeCosts(const Ctx& c) {
 			if (outside) { *costs++ = 255; continue; }
 			const float normSq1 = sumSq - (sum * sum) / sumWeights;
 			const float ncc = nom / pm_sqrtf(normSq0 * normSq1 + eps);
-			*costs++ = (ncc <= 0 ? (Cost)255 : (Cost)Round2Int((1.f - pm_minf(ncc, 1.f)) * 255.f));
+			*costs++ = sgmp_cost_of_ncc(ncc);          // the reference: ncc <= 0 ? 255 : ROUND2INT((1 - MINF(ncc, 1)) 255), the same for a finite ncc
 		}
 	}
 }

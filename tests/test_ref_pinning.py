@@ -252,10 +252,27 @@ def test_libm_build_bounds_the_pm_math_substitution(scene):
 
 
 # ---- SemiGlobalMatcher::Match (SemiGlobalMatcher.cpp:863-1302): cost volume, 8-path aggregation (threaded variant), winner-take-all -----------------
+def _hand_built_families():
+    """the families of tests/sgm_match_edge_cases.py inside the reference's domain (grey values in [0, 1], P1 <= P2, sums that fit 16 bits): the oracle is pinned where the
+    buffer edges, the packing, the ties and the penalty lookup decide, and not only the engine"""
+    from tests import sgm_match_edge_cases as ec
+    return sorted(f for f, (_, inside) in ec.FAMILIES.items() if inside)
+
+
 @pytest.mark.skipif(not pr.sgm_available(), reason="oracle/_ref/libref_sgm.so not built")
-@pytest.mark.parametrize("case", [(80, 60, 5, "uniform", 0, 16), (120, 90, 7, "ragged", 0, 24), (200, 150, 9, "holes", -4, 20), (96, 64, 3, "uniform", -8, 8), (160, 120, 11, "ragged", 0, 64)])
+@pytest.mark.parametrize("case", [(80, 60, 5, "uniform", 0, 16), (120, 90, 7, "ragged", 0, 24), (200, 150, 9, "holes", -4, 20), (96, 64, 3, "uniform", -8, 8), (160, 120, 11, "ragged", 0, 64)]
+                         + _hand_built_families())
 def test_sgm_match_is_the_reference_function(case):
     from tests import sgm_cases as scs
+    if isinstance(case, str):
+        from tests import sgm_match_edge_cases as ec
+        for p in ec.problems(case):
+            want = ec.prove(p)
+            for route, table in p.tables().items():
+                b = pr.ref_sgm_match(p.bgr, p.gl, p.gr, p.px, p.n, p.mxd, p.P1, table)
+                for x, y, nm in zip(want[route], b, ec.NAMES):
+                    assert np.array_equal(x, y), "%s, %s route: %s: %d differ" % (p.name, route, nm, int((x != y).sum()))
+        return
     w, h, shift, kind, lo, hi = case
     lb, lg, rg = scs.stereo_pair(w, h, shift, seed=3)
     px, n, mx = scs.ranges(w, h, kind, lo, hi)
