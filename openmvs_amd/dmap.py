@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import build as _build
+from . import _cabi, build as _build
 
 
 class DMapHeader(C.Structure):
@@ -15,16 +15,16 @@ class DMapHeader(C.Structure):
                 ("K", C.c_double * 9), ("R", C.c_double * 9), ("C", C.c_double * 3), ("imageFileName", C.c_char * 1024)]
 
 
-EXPORTS = ["dmap_write", "dmap_read_header", "dmap_read", "dimap_write", "dimap_read"]
+_TYPES = {"DMapHeader": DMapHeader}
+_SIGNATURES = _cabi.signatures("dmapio.h", _TYPES)
+EXPORTS = list(_SIGNATURES)          # every function include/dmapio.h declares
 _LIB = None
 
 
 def load_library():
     global _LIB
     if _LIB is None:
-        _LIB = C.CDLL(_build.build_host_lib("libdmapio.so"))
-        for n in EXPORTS:
-            getattr(_LIB, n)
+        _LIB = _cabi.declare(C.CDLL(_build.build_host_lib("libdmapio.so")), _SIGNATURES)
     return _LIB
 
 
@@ -42,10 +42,8 @@ def save(path, image_name, ids, image_size, K, R, Cc, dmin, dmax, depth, normal=
     h.nIDs = len(ids); h.IDs[:len(ids)] = [int(i) for i in ids]
     h.K[:] = np.asarray(K, np.float64).ravel(); h.R[:] = np.asarray(R, np.float64).ravel(); h.C[:] = np.asarray(Cc, np.float64).ravel()
     h.imageFileName = image_name.encode()
-    fp = lambda a, t: None if a is None else np.ascontiguousarray(a, t).ctypes.data_as(C.c_void_p)
-    keep = [None if a is None else np.ascontiguousarray(a, t) for a, t in ((normal, np.float32), (conf, np.float32), (views, np.uint8))]
-    rc = load_library().dmap_write(str(path).encode(), C.byref(h), depth.ctypes.data_as(C.c_void_p),
-                                   *[None if k is None else k.ctypes.data_as(C.c_void_p) for k in keep])
+    planes = [None if a is None else np.ascontiguousarray(a, t) for a, t in ((normal, np.float32), (conf, np.float32), (views, np.uint8))]
+    rc = load_library().dmap_write(str(path).encode(), C.byref(h), depth, *planes)
     if rc != 0:
         raise IOError("dmap_write failed: %d" % rc)
 
@@ -65,8 +63,7 @@ def load(path, flags: int = 15) -> dict:
     n = np.zeros((hh, ww, 3), np.float32) if (h.type & 2 and flags & 2) else None
     c = np.zeros((hh, ww), np.float32) if (h.type & 4 and flags & 4) else None
     v = np.zeros((hh, ww, 4), np.uint8) if (h.type & 8 and flags & 8) else None
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    rc = lib.dmap_read(str(path).encode(), C.byref(h), C.c_uint(flags), p(d), p(n), p(c), p(v))
+    rc = lib.dmap_read(str(path).encode(), C.byref(h), flags, d, n, c, v)
     if rc != 0:
         raise IOError("dmap_read failed: %d" % rc)
     for k, a in (("depth_map", d), ("normal_map", n), ("confidence_map", c), ("views_map", v)):
@@ -80,8 +77,7 @@ def save_dimap(path, image_size, H, Q, subpixel_steps, disparity, cost=None):
     """SemiGlobalMatcher::ExportDisparityDataRawFull (libs/MVS/SemiGlobalMatcher.cpp:2124-2138): valid-grid maps in, bordered maps on disk."""
     d = np.ascontiguousarray(disparity, np.int16); c = None if cost is None else np.ascontiguousarray(cost, np.uint16)
     hh = np.ascontiguousarray(H, np.float64); qq = np.ascontiguousarray(Q, np.float64)
-    rc = load_library().dimap_write(str(path).encode(), int(image_size[0]), int(image_size[1]), hh.ctypes.data_as(C.POINTER(C.c_double)), qq.ctypes.data_as(C.POINTER(C.c_double)),
-                                    C.c_int16(subpixel_steps), d.ctypes.data_as(C.c_void_p), None if c is None else c.ctypes.data_as(C.c_void_p), d.shape[1], d.shape[0])
+    rc = load_library().dimap_write(str(path).encode(), image_size[0], image_size[1], hh, qq, subpixel_steps, d, c, d.shape[1], d.shape[0])
     if rc != 0:
         raise IOError("dimap_write failed: %d" % rc)
 
@@ -91,11 +87,10 @@ def load_dimap(path) -> dict:
     lib = load_library()
     iw, ih, w, h, hc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(); st = C.c_int16()
     H = np.zeros((3, 3)); Q = np.zeros((4, 4))
-    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-    args = (str(path).encode(), C.byref(iw), C.byref(ih), dp(H), dp(Q), C.byref(st), C.byref(w), C.byref(h), C.byref(hc))
+    args = (str(path).encode(), C.byref(iw), C.byref(ih), H, Q, C.byref(st), C.byref(w), C.byref(h), C.byref(hc))
     if lib.dimap_read(*args, None, None) != 0:
         raise IOError("invalid disparity-data file '%s'" % path)
     d = np.zeros((h.value, w.value), np.int16); c = np.zeros((h.value, w.value), np.uint16) if hc.value else None
-    if lib.dimap_read(*args, d.ctypes.data_as(C.c_void_p), None if c is None else c.ctypes.data_as(C.c_void_p)) != 0:
+    if lib.dimap_read(*args, d, c) != 0:
         raise IOError("dimap_read failed")
     return dict(image_size=(iw.value, ih.value), H=H, Q=Q, subpixel_steps=int(st.value), disparity=d, cost=c)

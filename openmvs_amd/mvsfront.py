@@ -6,12 +6,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import build as _build
+from . import _cabi, build as _build
 
 VIEW_SCORE_DTYPE = np.dtype([("ID", "<u4"), ("points", "<u4"), ("scale", "<f4"), ("angle", "<f4"), ("area", "<f4"), ("score", "<f4")])
-EXPORTS = ["mvsf_default_options", "mvsf_load", "mvsf_free", "mvsf_version", "mvsf_num_images", "mvsf_num_points", "mvsf_image_info", "mvsf_point",
-           "mvsf_camera", "mvsf_select_views", "mvsf_select_neighbor_views", "mvsf_init_depth_map", "mvsf_init_depth_map_dense", "mvsf_triangulate_depth_map",
-           "mvsf_get_neighbors", "mvsf_set_neighbors", "mvsf_load_view_neighbors", "mvsf_save_view_neighbors", "mvsf_image_depths", "mvsf_estimate_normal_map"]
 
 
 class MVSFOptions(C.Structure):
@@ -19,17 +16,16 @@ class MVSFOptions(C.Structure):
                 ("fViewMinScore", C.c_float), ("fViewMinScoreRatio", C.c_float), ("fMinArea", C.c_float), ("fMinAngle", C.c_float), ("fOptimAngle", C.c_float), ("fMaxAngle", C.c_float)]
 
 
+_TYPES = {"MVSFViewScore": VIEW_SCORE_DTYPE, "MVSFOptions": MVSFOptions}          # the mirrors by their names in include/mvsfront.h
+_SIGNATURES = _cabi.signatures("mvsfront.h", _TYPES)
+EXPORTS = list(_SIGNATURES)          # every function include/mvsfront.h declares
 _LIB = None
 
 
 def load_library() -> C.CDLL:
     global _LIB
     if _LIB is None:
-        lib = C.CDLL(_build.build_host_lib("libmvsfront.so"))
-        lib.mvsf_free.restype = None; lib.mvsf_default_options.restype = None
-        for n in EXPORTS:
-            getattr(lib, n)
-        _LIB = lib
+        _LIB = _cabi.declare(C.CDLL(_build.build_host_lib("libmvsfront.so")), _SIGNATURES)
     return _LIB
 
 
@@ -65,13 +61,12 @@ class SceneFront:
 
     def point(self, i):
         X = np.zeros(3, np.float32); n = C.c_int(); views = np.zeros(64, np.uint32)
-        assert self._lib.mvsf_point(self._h, i, X.ctypes.data_as(C.POINTER(C.c_float)), views.ctypes.data_as(C.POINTER(C.c_uint32)), 64, C.byref(n)) == 0
+        assert self._lib.mvsf_point(self._h, i, X, views, 64, C.byref(n)) == 0
         return X, views[:n.value].copy()
 
     def camera(self, i, size=(0, 0)):
         K = np.zeros((3, 3)); R = np.zeros((3, 3)); Cc = np.zeros(3)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        rc = self._lib.mvsf_camera(self._h, i, int(size[0]), int(size[1]), dp(K), dp(R), dp(Cc))
+        rc = self._lib.mvsf_camera(self._h, i, size[0], size[1], K, R, Cc)
         if rc != 0:
             raise ValueError("mvsf_camera failed: %d" % rc)
         return K, R, Cc
@@ -81,12 +76,12 @@ class SceneFront:
         n = C.c_int()
         assert self._lib.mvsf_get_neighbors(self._h, i, None, 0, C.byref(n)) == 0
         nb = np.zeros(n.value, VIEW_SCORE_DTYPE)
-        assert self._lib.mvsf_get_neighbors(self._h, i, nb.ctypes.data_as(C.c_void_p), len(nb), C.byref(n)) == 0
+        assert self._lib.mvsf_get_neighbors(self._h, i, nb, len(nb), C.byref(n)) == 0
         return nb
 
     def set_neighbors(self, i, nb):
         nb = np.ascontiguousarray(nb, VIEW_SCORE_DTYPE)
-        if self._lib.mvsf_set_neighbors(self._h, i, nb.ctypes.data_as(C.c_void_p), len(nb)) != 0:
+        if self._lib.mvsf_set_neighbors(self._h, i, nb, len(nb)) != 0:
             raise ValueError("mvsf_set_neighbors(%d)" % i)
 
     def load_view_neighbors(self, path: str):
@@ -104,24 +99,17 @@ class SceneFront:
         assert self._lib.mvsf_image_depths(self._h, i, C.byref(a), C.byref(b), C.byref(c)) == 0
         return a.value, b.value, c.value
 
-    def _sizes(self, sizes):
-        if sizes is None:
-            return None, None
-        a = np.ascontiguousarray(sizes, np.int32).reshape(-1)
-        return a, a.ctypes.data_as(C.POINTER(C.c_int))
-
     def select_neighbor_views(self, i, nMinViews=2, nMinPointViews=2, fOptimAngle=12.0, nInsideROI=1, sizes=None):
         nb = np.zeros(self.n_images, VIEW_SCORE_DTYPE); pts = np.zeros(self.n_points, np.uint32); nn = C.c_int(); npts = C.c_int(); avg = C.c_float()
-        keep, ps = self._sizes(sizes)
-        rc = self._lib.mvsf_select_neighbor_views(self._h, i, ps, nMinViews, nMinPointViews, C.c_float(fOptimAngle), nInsideROI, nb.ctypes.data_as(C.c_void_p), len(nb), C.byref(nn),
-                                                  pts.ctypes.data_as(C.POINTER(C.c_uint32)), len(pts), C.byref(npts), C.byref(avg))
+        ps = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
+        rc = self._lib.mvsf_select_neighbor_views(self._h, i, ps, nMinViews, nMinPointViews, fOptimAngle, nInsideROI, nb, len(nb), C.byref(nn), pts, len(pts), C.byref(npts), C.byref(avg))
         return rc == 0, nb[:nn.value].copy(), pts[:npts.value].copy(), float(avg.value)
 
     def select_views(self, i, opt=None, sizes=None):
         opt = opt or default_options()
         nb = np.zeros(self.n_images, VIEW_SCORE_DTYPE); pts = np.zeros(self.n_points, np.uint32); nn = C.c_int(); npts = C.c_int(); avg = C.c_float()
-        keep, ps = self._sizes(sizes)
-        rc = self._lib.mvsf_select_views(self._h, i, ps, C.byref(opt), nb.ctypes.data_as(C.c_void_p), len(nb), C.byref(nn), pts.ctypes.data_as(C.POINTER(C.c_uint32)), len(pts), C.byref(npts), C.byref(avg))
+        ps = None if sizes is None else np.ascontiguousarray(sizes, np.int32)
+        rc = self._lib.mvsf_select_views(self._h, i, ps, C.byref(opt), nb, len(nb), C.byref(nn), pts, len(pts), C.byref(npts), C.byref(avg))
         if rc != 0:
             return None
         return nb[:nn.value].copy(), pts[:npts.value].copy(), float(avg.value)
@@ -131,11 +119,10 @@ class SceneFront:
         w, h = size
         d = np.zeros((h, w), np.float32); n = np.zeros((h, w, 3), np.float32); dmin = C.c_float(); dmax = C.c_float()
         p = np.ascontiguousarray(points, np.uint32)
-        out = (d.ctypes.data_as(C.POINTER(C.c_float)), n.ctypes.data_as(C.POINTER(C.c_float)), C.byref(dmin), C.byref(dmax))
         if dense:
-            rc = self._lib.mvsf_init_depth_map_dense(self._h, i, w, h, p.ctypes.data_as(C.POINTER(C.c_uint32)), len(p), *out)
+            rc = self._lib.mvsf_init_depth_map_dense(self._h, i, w, h, p, len(p), d, n, C.byref(dmin), C.byref(dmax))
         else:
-            rc = self._lib.mvsf_init_depth_map(self._h, i, w, h, p.ctypes.data_as(C.POINTER(C.c_uint32)), len(p), nMinViewsTrustPoint, *out)
+            rc = self._lib.mvsf_init_depth_map(self._h, i, w, h, p, len(p), nMinViewsTrustPoint, d, n, C.byref(dmin), C.byref(dmax))
         if rc != 0:
             raise ValueError("mvsf_init_depth_map failed: %d" % rc)
         return d, n, float(dmin.value), float(dmax.value)
@@ -145,8 +132,7 @@ class SceneFront:
         w, h = size
         d = np.zeros((h, w), np.float32); dmin = C.c_float(); dmax = C.c_float()
         p = np.ascontiguousarray(points, np.uint32)
-        rc = self._lib.mvsf_triangulate_depth_map(self._h, i, w, h, p.ctypes.data_as(C.POINTER(C.c_uint32)), len(p), int(avg_depth is not None),
-                                                  C.c_float(avg_depth or 0.0), int(sparse), d.ctypes.data_as(C.POINTER(C.c_float)), C.byref(dmin), C.byref(dmax))
+        rc = self._lib.mvsf_triangulate_depth_map(self._h, i, w, h, p, len(p), avg_depth is not None, avg_depth or 0.0, bool(sparse), d, C.byref(dmin), C.byref(dmax))
         if rc != 0:
             raise ValueError("mvsf_triangulate_depth_map failed: %d" % rc)
         return d, float(dmin.value), float(dmax.value)
@@ -157,7 +143,7 @@ def estimate_normal_map(K, depth):
     d = np.ascontiguousarray(depth, np.float32); h, w = d.shape
     k = np.ascontiguousarray(np.asarray(K, np.float64).ravel())
     out = np.zeros((h, w, 3), np.float32)
-    rc = load_library().mvsf_estimate_normal_map(k.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_float)), w, h, out.ctypes.data_as(C.POINTER(C.c_float)))
+    rc = load_library().mvsf_estimate_normal_map(k, d, w, h, out)
     if rc != 0:
         raise ValueError("mvsf_estimate_normal_map: %d" % rc)
     return out

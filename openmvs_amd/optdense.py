@@ -11,7 +11,8 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import mvsfront as _front
+from . import _cabi, mvsfront as _front
+from .patchmatch import PMHipParams
 
 _U, _I, _F = C.c_uint32, C.c_int32, C.c_float
 
@@ -52,7 +53,6 @@ class OptDense(C.Structure):
 
     def params(self, seed: int = 0):
         """PMHipParams for the estimator (the seed is ours: the reference seeds from random_device)."""
-        from .patchmatch import PMHipParams
         p = PMHipParams()
         _lib().mvsf_optdense_estimator(C.byref(self), C.byref(p))       # every field but the seed
         p.seed = seed
@@ -70,22 +70,20 @@ class OptDense(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+_TYPES = {"MVSFOptDense": OptDense, "MVSFOptions": _front.MVSFOptions, "PMHipParams": PMHipParams}
+_SIGNATURES = _cabi.signatures("optdense.h", _TYPES)
+EXPORTS = list(_SIGNATURES)          # every function include/optdense.h declares
 _READY = False
 
 
 def _lib():
+    """libmvsfront.so with the signatures of include/optdense.h declared as well."""
     global _READY
     lib = _front.load_library()
     if not _READY:
-        lib.mvsf_optdense_init.restype = None; lib.mvsf_optdense_front.restype = None; lib.mvsf_optdense_estimator.restype = None
-        for n in EXPORTS:
-            getattr(lib, n)
+        _cabi.declare(lib, _SIGNATURES)
         _READY = True
     return lib
-
-
-EXPORTS = ["mvsf_optdense_count", "mvsf_optdense_describe", "mvsf_optdense_init", "mvsf_optdense_set", "mvsf_optdense_get", "mvsf_optdense_load", "mvsf_optdense_save",
-           "mvsf_optdense_front", "mvsf_optdense_estimator"]
 
 
 def defaults() -> OptDense:

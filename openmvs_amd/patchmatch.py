@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from . import build as _build
+from . import _cabi, build as _build
 
 MAX_SOURCES = 16
 
@@ -72,12 +72,9 @@ class PMHipTuning(C.Structure):
     _fields_ = [("viewGroups", C.c_int32), ("wideMaxViews", C.c_int32), ("wideHyps", C.c_int32), ("sweepLanes", C.c_int32), ("quadBuffer", C.c_int32), ("widePixels", C.c_int32), ("wide8Pixels", C.c_int32), ("reserved0", C.c_int32)]
 
 
-EXPORTS = ["pmhip_working_size", "pmhip_scaled_size", "pmhip_image_prepare", "pmhip_image_scale", "pmhip_image_get", "pmhip_image_drop", "pmhip_image_bytes", "pmhip_image_stats_get", "pmhip_scene_set_view_stored",
-           "pmhip_get_tuning", "pmhip_set_tuning", "pmhip_scene_set_view_id", "pmhip_scene_set_view_sized", "pmhip_scene_set_source_depth", "pmhip_scene_set_mask", "pmhip_scene_set_mask_mode", "pmhip_scene_set_conf", "pmhip_scene_set_color", "pmhip_scene_fuse", "pmhip_scene_fuse_get", "pmhip_scene_fuse_rounds", "pmhip_scene_cloud_finish", "pmhip_scene_cloud_set", "pmhip_scene_cloud_knn", "pmhip_scene_cloud_times", "pmhip_scene_cloud_load", "pmhip_scene_cloud_filter", "pmhip_scene_cloud_visibility", "pmhip_scene_cloud_filter_cones", "pmhip_scene_cloud_filter_times", "pmhip_scene_cloud_filter_counts", "pmhip_default_params", "pmhip_create", "pmhip_destroy", "pmhip_init", "pmhip_release",
-           "pmhip_estimate_depth_map", "pmhip_estimate_depth_map_masked", "pmhip_last_error", "pmhip_scene_create", "pmhip_scene_set_view",
-           "pmhip_scene_estimate", "pmhip_scene_commit_round", "pmhip_scene_reset_view", "pmhip_scene_set_maps",
-           "pmhip_scene_get_maps", "pmhip_scene_device_ptr", "pmhip_scene_copy", "pmhip_scene_filter", "pmhip_scene_filter_commit", "pmhip_scene_gap_interpolation", "pmhip_scene_remove_small_segments", "pmhip_scene_images_updated", "pmhip_scene_maps_updated", "pmhip_scene_bytes", "pmhip_sync",
-           "pmhip_stream", "pmhip_stats_reset", "pmhip_stats_get", "pmhip_prof_get", "pmhip_math_eval", "pmhip_resize", "pmhip_resample", "pmhip_set_sweep_tiles", "pmhip_abi_version"]
+_TYPES = {c.__name__: c for c in (PMHipParams, PMHipView, PMHipDepthData, PMHipKernelStats, PMHipFuseParams, PMHipCloudParams, PMHipCloudFilterParams, PMHipImageStats, PMHipTuning)}
+_SIGNATURES = _cabi.signatures("pmhip.h", _TYPES)
+EXPORTS = list(_SIGNATURES)          # every function include/pmhip.h declares
 
 _LIB = None
 
@@ -93,19 +90,8 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "hipemu_counters") and os.environ.get("OPENMVS_AMD_TEST_EMULATOR") != "1":
             # tests/cpp/hipemu builds of the kernels exist for the CPU test-suite only; the product never computes on the host
             raise RuntimeError("%s is a CPU-emulated test build, not a device library: refusing to load it outside the test-suite" % path)
-        lib.pmhip_last_error.restype = C.c_char_p
-        lib.pmhip_scene_device_ptr.restype = C.c_void_p
-        lib.pmhip_stream.restype = C.c_void_p
-        lib.pmhip_destroy.restype = None
-        lib.pmhip_scene_fuse_rounds.restype = C.c_uint64
-        if hasattr(lib, "pmhip_image_bytes"):
-            lib.pmhip_image_bytes.restype = C.c_uint64
-        experiment = bool(os.environ.get("PMHIP_LIB"))        # (an older build of the library in an A/B run may lack the newest entry points)
-        for n in EXPORTS:
-            if not (experiment and (n in ("pmhip_resample", "pmhip_set_sweep_tiles", "pmhip_abi_version", "pmhip_working_size", "pmhip_scaled_size", "pmhip_scene_set_view_stored") or n.startswith("pmhip_image_"))):
-                getattr(lib, n)  # raises AttributeError if a declared symbol is missing
-        if hasattr(lib, "pmhip_abi_version"):
-            lib.pmhip_abi_version.restype = C.c_uint32
+        experiment = bool(os.environ.get("PMHIP_LIB"))        # (an older build of the library in an A/B run may lack some entry points; otherwise a missing one raises)
+        _cabi.declare(lib, _SIGNATURES, allow_missing=experiment)
         if hasattr(lib, "pmhip_abi_version") and lib.pmhip_abi_version() != PMHIP_ABI_VERSION and not experiment:
             raise RuntimeError("%s has struct layout version %d, these bindings are written for %d (include/pmhip.h)" % (path, lib.pmhip_abi_version(), PMHIP_ABI_VERSION))
         _LIB = lib
@@ -123,7 +109,7 @@ def default_params(**kw) -> PMHipParams:
 def working_size(W0: int, H0: int, n_resolution_level: int = 1, n_min_resolution: int = 640, n_max_resolution: int = 0):
     """pmhip_working_size: the (w, h) an image of W0 x H0 is brought to (`views.compute_max_resolution` + `views.resized_size`).  Needs no device."""
     w, h = C.c_int(), C.c_int()
-    rc = load_library().pmhip_working_size(int(W0), int(H0), C.c_uint(int(n_resolution_level)), C.c_uint(int(n_min_resolution)), C.c_uint(int(n_max_resolution)), C.byref(w), C.byref(h))
+    rc = load_library().pmhip_working_size(W0, H0, n_resolution_level, n_min_resolution, n_max_resolution, C.byref(w), C.byref(h))
     if rc != 0:
         raise ValueError("pmhip_working_size(%d, %d): error %d" % (W0, H0, rc))
     return w.value, h.value
@@ -132,18 +118,7 @@ def working_size(W0: int, H0: int, n_resolution_level: int = 1, n_min_resolution
 def scaled_size(W: int, H: int, scale):
     """pmhip_scaled_size: the (w, h) of `ScaleImage(scale)` of a W x H image, or None when `NeedScaleImage` is false.  Needs no device."""
     w, h = C.c_int(), C.c_int()
-    return (w.value, h.value) if load_library().pmhip_scaled_size(int(W), int(H), C.c_float(float(np.float32(scale))), C.byref(w), C.byref(h)) else None
-
-
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _dp(a):
-    """float64 array -> double* (the array is kept alive by ctypes for the duration of the call)."""
-    a = np.ascontiguousarray(a, np.float64)
-    p = a.ctypes.data_as(C.POINTER(C.c_double)); p._keep = a
-    return p
+    return (w.value, h.value) if load_library().pmhip_scaled_size(W, H, scale, C.byref(w), C.byref(h)) else None
 
 
 class PatchMatchError(RuntimeError):
@@ -156,7 +131,10 @@ class PatchMatchHIP:
     def __init__(self, device: int = 0):
         self._lib = load_library()
         self._h = C.c_void_p()
-        rc = self._lib.pmhip_create(C.c_int(device), C.byref(self._h))
+        self._scene = None        # (n_images, w, h) of scene_create
+        self._sizes = {}          # slot -> (w, h) of a view with its own size
+        self._images = {}         # image-store key -> (w, h, has colour)
+        rc = self._lib.pmhip_create(device, C.byref(self._h))
         if rc != 0:
             raise PatchMatchError(f"pmhip_create failed ({rc}): no usable MI355X / HIP device")
         self.params = default_params()
@@ -167,7 +145,7 @@ class PatchMatchHIP:
 
     # -- the four reference methods ---------------------------------------------------------
     def Init(self, bGeomConsistency: bool):
-        self._chk(self._lib.pmhip_init(self._h, C.c_int(1 if bGeomConsistency else 0)))
+        self._chk(self._lib.pmhip_init(self._h, bool(bGeomConsistency)))
 
     def Release(self):
         if self._h:
@@ -186,12 +164,12 @@ class PatchMatchHIP:
         for k, i in enumerate(ids):
             img = np.ascontiguousarray(gray[i], np.float32); keep.append(img)
             v = views[k]
-            v.image = _fp(img); v.h, v.w = img.shape
+            v.image = img.ctypes.data_as(C.POINTER(C.c_float)); v.h, v.w = img.shape
             v.K[:] = np.asarray(K[i], np.float64).ravel(); v.R[:] = np.asarray(R[i], np.float64).ravel(); v.C[:] = np.asarray(Cc[i], np.float64).ravel()
             v.id = int(i)
             if k > 0 and src_depths is not None:
                 d = np.ascontiguousarray(src_depths[i], np.float32); keep.append(d)
-                v.depth = _fp(d); v.dh, v.dw = d.shape
+                v.depth = d.ctypes.data_as(C.POINTER(C.c_float)); v.dh, v.dw = d.shape
                 if src_depth_cams is not None and i in src_depth_cams:
                     kd, rd, cd = src_depth_cams[i]
                     v.Kd[:] = np.asarray(kd, np.float64).ravel(); v.Rd[:] = np.asarray(rd, np.float64).ravel(); v.Cd[:] = np.asarray(cd, np.float64).ravel()
@@ -201,15 +179,14 @@ class PatchMatchHIP:
         depth = np.zeros((h, w), np.float32) if depth is None else np.ascontiguousarray(depth, np.float32).copy()
         normal = np.zeros((h, w, 3), np.float32) if normal is None else np.ascontiguousarray(normal, np.float32).copy()
         conf = np.zeros((h, w), np.float32)
-        dd = PMHipDepthData(views, n, _fp(depth), _fp(normal), _fp(conf), float(dmin), float(dmax))
+        dd = PMHipDepthData(views, n, *(a.ctypes.data_as(C.POINTER(C.c_float)) for a in (depth, normal, conf)), float(dmin), float(dmax))
         if mask is None and not mask_option:
-            self._chk(self._lib.pmhip_estimate_depth_map(self._h, C.byref(dd), C.byref(p), C.c_int(nGeometricIter)))
+            self._chk(self._lib.pmhip_estimate_depth_map(self._h, C.byref(dd), C.byref(p), nGeometricIter))
         else:
             m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
             if m is not None and m.shape != (h, w):
                 raise ValueError("mask must have the reference view's size")
-            self._chk(self._lib.pmhip_estimate_depth_map_masked(self._h, C.byref(dd), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                                1 if mask_option else 0, C.byref(p), C.c_int(nGeometricIter)))
+            self._chk(self._lib.pmhip_estimate_depth_map_masked(self._h, C.byref(dd), m, bool(mask_option), C.byref(p), nGeometricIter))
         return depth, normal, conf
 
     # -- HBM-resident scene interface --------------------------------------------------------
@@ -220,17 +197,10 @@ class PatchMatchHIP:
     def scene_set_view(self, idx, gray, K, R, Cc, dmin, dmax, neighbors, device_ptr=None):
         K = np.ascontiguousarray(K, np.float64); R = np.ascontiguousarray(R, np.float64); Cc = np.ascontiguousarray(Cc, np.float64)
         nb = np.ascontiguousarray(neighbors, np.int32)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        if device_ptr is not None:
-            src, ondev = C.cast(C.c_void_p(device_ptr), C.POINTER(C.c_float)), 1
-        elif gray is None:
-            src, ondev = None, 0
-        else:
-            g = np.ascontiguousarray(gray, np.float32); src, ondev = _fp(g), 0
+        src = device_ptr if device_ptr is not None else None if gray is None else np.ascontiguousarray(gray, np.float32)
         if src is not None:
-            getattr(self, "_sizes", {}).pop(int(idx), None)       # (an image of the scene's size takes the view back into the scene arrays)
-        self._chk(self._lib.pmhip_scene_set_view(self._h, idx, src, ondev, dp(K), dp(R), dp(Cc), C.c_float(dmin), C.c_float(dmax),
-                                                 nb.ctypes.data_as(C.POINTER(C.c_int32)), len(nb)))
+            self._sizes.pop(int(idx), None)       # (an image of the scene's size takes the view back into the scene arrays)
+        self._chk(self._lib.pmhip_scene_set_view(self._h, idx, src, device_ptr is not None, K, R, Cc, dmin, dmax, nb, len(nb)))
 
     def tuning(self, **kw):
         """pmhip_get_tuning / pmhip_set_tuning: how a batch is mapped onto the GPU (viewGroups, wideMaxViews, wideHyps, sweepLanes, quadBuffer, widePixels, wide8Pixels); returns the settings
@@ -249,11 +219,11 @@ class PatchMatchHIP:
     def set_sweep_tiles(self, tile_w: int = 0, tile_h: int = 0):
         """OPT-IN, not the reference's estimator (pmhip_set_sweep_tiles): sweeps run inside tile_w x tile_h tiles, neighbours across a tile border are read as the previous
         sweep left them.  0, 0 = off (the reference's sweep, bit for bit).  The result equals the oracle's with tileW / tileH set."""
-        self._chk(self._lib.pmhip_set_sweep_tiles(self._h, int(tile_w), int(tile_h)))
+        self._chk(self._lib.pmhip_set_sweep_tiles(self._h, tile_w, tile_h))
 
     def scene_set_view_id(self, idx, view_id):
         """The identity slot idx draws its random numbers under (pmhip_scene_set_view_id): the view's index in the whole scene when this engine holds a part of it."""
-        self._chk(self._lib.pmhip_scene_set_view_id(self._h, int(idx), C.c_uint32(int(view_id))))
+        self._chk(self._lib.pmhip_scene_set_view_id(self._h, idx, view_id))
 
     def scene_load(self, scene, n_levels=2, drop_stored=True):
         """Upload a synth.Scene (or anything with the same attributes).  Slots listed in `scene.stored` ({slot: key}; densify.load_scene(..., engine=self)) adopt their
@@ -281,10 +251,10 @@ class PatchMatchHIP:
     def scene_set_view_sized(self, idx, gray, K, R, Cc, dmin, dmax, neighbors):
         """A view whose image -- and therefore its depth, normal and confidence maps -- has its own size (pmhip_scene_set_view_sized): a source view or a reference view."""
         g = np.ascontiguousarray(gray, np.float32)
-        self._sizes = getattr(self, "_sizes", {}); self._sizes[int(idx)] = (g.shape[1], g.shape[0])
+        self._sizes[int(idx)] = (g.shape[1], g.shape[0])
+        K = np.ascontiguousarray(K, np.float64); R = np.ascontiguousarray(R, np.float64); Cc = np.ascontiguousarray(Cc, np.float64)
         nb = np.ascontiguousarray(neighbors, np.int32)
-        self._chk(self._lib.pmhip_scene_set_view_sized(self._h, idx, _fp(g), g.shape[1], g.shape[0], 0, _dp(K), _dp(R), _dp(Cc), C.c_float(dmin), C.c_float(dmax),
-                                                       nb.ctypes.data_as(C.POINTER(C.c_int32)), len(nb)))
+        self._chk(self._lib.pmhip_scene_set_view_sized(self._h, idx, g, g.shape[1], g.shape[0], False, K, R, Cc, dmin, dmax, nb, len(nb)))
 
     # -- the image store: working-resolution images made on the device (include/pmhip.h, section 2b) ---------------------------------
     def image_prepare(self, key, img, w, h, channel_order=1):
@@ -293,34 +263,34 @@ class PatchMatchHIP:
         a = np.ascontiguousarray(img, np.uint8)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("img must be (h, w, 3) uint8")
-        self._chk(self._lib.pmhip_image_prepare(self._h, int(key), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0], int(channel_order), int(w), int(h)))
-        self._images = getattr(self, "_images", {}); self._images[int(key)] = (int(w), int(h), True)
+        self._chk(self._lib.pmhip_image_prepare(self._h, key, a, a.shape[1], a.shape[0], channel_order, w, h))
+        self._images[int(key)] = (int(w), int(h), True)
 
     def image_scale(self, key, src_key, scale):
         """Entry `key` gets `ScaleImage(gray of entry src_key, scale)`, gray only (pmhip_image_scale: `densify.scale_image`); returns its (w, h)."""
         w, h = C.c_int(), C.c_int()
-        self._chk(self._lib.pmhip_image_scale(self._h, int(key), int(src_key), C.c_float(float(np.float32(scale))), C.byref(w), C.byref(h)))
-        self._images = getattr(self, "_images", {}); self._images[int(key)] = (w.value, h.value, False)
+        self._chk(self._lib.pmhip_image_scale(self._h, key, src_key, scale, C.byref(w), C.byref(h)))
+        self._images[int(key)] = (w.value, h.value, False)
         return w.value, h.value
 
     def image_get(self, key):
         """(gray (h, w) float32, bgr (h, w, 3) uint8 or None for a gray-only entry) of entry `key` (pmhip_image_get)."""
         w, h = C.c_int(), C.c_int()
-        self._chk(self._lib.pmhip_image_get(self._h, int(key), C.byref(w), C.byref(h), None, None))
+        self._chk(self._lib.pmhip_image_get(self._h, key, C.byref(w), C.byref(h), None, None))
         gray = np.zeros((h.value, w.value), np.float32)
-        self._chk(self._lib.pmhip_image_get(self._h, int(key), None, None, _fp(gray), None))
+        self._chk(self._lib.pmhip_image_get(self._h, key, None, None, gray, None))
         bgr = np.zeros((h.value, w.value, 3), np.uint8)
-        if self._lib.pmhip_image_get(self._h, int(key), None, None, None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
+        if self._lib.pmhip_image_get(self._h, key, None, None, None, bgr) != 0:
             bgr = None
         return gray, bgr
 
     def image_drop(self, key=-1):
         """Free entry `key` of the image store; key < 0: everything (pmhip_image_drop)."""
-        self._chk(self._lib.pmhip_image_drop(self._h, int(key)))
+        self._chk(self._lib.pmhip_image_drop(self._h, key))
         if int(key) < 0:
             self._images = {}
         else:
-            getattr(self, "_images", {}).pop(int(key), None)
+            self._images.pop(int(key), None)
 
     def image_bytes(self) -> int:
         """Device memory the image store holds right now (pmhip_image_bytes)."""
@@ -329,20 +299,19 @@ class PatchMatchHIP:
     def image_stats(self, reset=False) -> dict:
         """pmhip_image_stats_get: images prepared / resampled, bytes of decoded images uploaded, kernel time by HIP events and upload time, in ms."""
         s = PMHipImageStats()
-        self._chk(self._lib.pmhip_image_stats_get(self._h, C.byref(s), 1 if reset else 0))
+        self._chk(self._lib.pmhip_image_stats_get(self._h, C.byref(s), bool(reset)))
         return dict(prepared=int(s.nPrepared), scaled=int(s.nScaled), bytes_uploaded=int(s.bytesUploaded), kernel_ms=float(s.kernelMs), upload_ms=float(s.uploadMs))
 
     def scene_set_view_stored(self, idx, key, K, R, Cc, dmin, dmax, neighbors):
         """scene_set_view / scene_set_view_sized (by the entry's size) with the stored gray image of entry `key`, read on the device, and its colour image if it has one
         (pmhip_scene_set_view_stored).  The view holds copies."""
+        K = np.ascontiguousarray(K, np.float64); R = np.ascontiguousarray(R, np.float64); Cc = np.ascontiguousarray(Cc, np.float64)
         nb = np.ascontiguousarray(neighbors, np.int32)
-        self._chk(self._lib.pmhip_scene_set_view_stored(self._h, int(idx), int(key), _dp(K), _dp(R), _dp(Cc), C.c_float(dmin), C.c_float(dmax),
-                                                        nb.ctypes.data_as(C.POINTER(C.c_int32)), len(nb)))
-        w, h, _ = getattr(self, "_images", {}).get(int(key), (None, None, False))
+        self._chk(self._lib.pmhip_scene_set_view_stored(self._h, idx, key, K, R, Cc, dmin, dmax, nb, len(nb)))
+        w, h, _ = self._images.get(int(key), (None, None, False))
         if w is None:                                          # (an entry made through the C ABI directly)
             cw, ch = C.c_int(), C.c_int()
-            self._chk(self._lib.pmhip_image_get(self._h, int(key), C.byref(cw), C.byref(ch), None, None)); w, h = cw.value, ch.value
-        self._sizes = getattr(self, "_sizes", {})
+            self._chk(self._lib.pmhip_image_get(self._h, key, C.byref(cw), C.byref(ch), None, None)); w, h = cw.value, ch.value
         if (w, h) == tuple(self._scene[1:]):
             self._sizes.pop(int(idx), None)
         else:
@@ -353,13 +322,13 @@ class PatchMatchHIP:
         if depth is None:
             self._chk(self._lib.pmhip_scene_set_source_depth(self._h, idx, None, 0, 0, None, None, None)); return
         d = np.ascontiguousarray(depth, np.float32)
-        self._chk(self._lib.pmhip_scene_set_source_depth(self._h, idx, _fp(d), d.shape[1], d.shape[0], _dp(Kd), _dp(Rd), _dp(Cd)))
+        Kd = np.ascontiguousarray(Kd, np.float64); Rd = np.ascontiguousarray(Rd, np.float64); Cd = np.ascontiguousarray(Cd, np.float64)
+        self._chk(self._lib.pmhip_scene_set_source_depth(self._h, idx, d, d.shape[1], d.shape[0], Kd, Rd, Cd))
 
     def scene_estimate(self, view_ids, nGeometricIter=-1, params=None, sync=True):
         ids = np.ascontiguousarray(view_ids, np.int32)
         p = params or self.params
-        self._chk(self._lib.pmhip_scene_estimate(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(p),
-                                                 C.c_int(nGeometricIter), C.c_int(1 if sync else 0)))
+        self._chk(self._lib.pmhip_scene_estimate(self._h, ids, len(ids), C.byref(p), nGeometricIter, bool(sync)))
 
     def scene_commit_round(self):
         self._chk(self._lib.pmhip_scene_commit_round(self._h))
@@ -370,7 +339,7 @@ class PatchMatchHIP:
     def scene_set_maps(self, idx, depth=None, normal=None):
         d = None if depth is None else np.ascontiguousarray(depth, np.float32)
         n = None if normal is None else np.ascontiguousarray(normal, np.float32)
-        self._chk(self._lib.pmhip_scene_set_maps(self._h, idx, _fp(d) if d is not None else None, _fp(n) if n is not None else None))
+        self._chk(self._lib.pmhip_scene_set_maps(self._h, idx, d, n))
 
     def scene_set_mask(self, idx, mask):
         """Ignore mask of a view: (h, w) array, 0 = ignore the pixel (--ignore-mask-label); None removes it."""
@@ -380,24 +349,24 @@ class PatchMatchHIP:
         w, h = self.view_size(idx)
         if m.shape != (h, w):
             raise ValueError("mask must be (h, w)")
-        self._chk(self._lib.pmhip_scene_set_mask(self._h, idx, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._chk(self._lib.pmhip_scene_set_mask(self._h, idx, m))
 
     def scene_set_mask_mode(self, mode):
-        self._chk(self._lib.pmhip_scene_set_mask_mode(self._h, int(mode)))
+        self._chk(self._lib.pmhip_scene_set_mask_mode(self._h, mode))
 
     def scene_set_conf(self, idx, conf):
         c = np.ascontiguousarray(conf, np.float32)
-        self._chk(self._lib.pmhip_scene_set_conf(self._h, idx, _fp(c)))
+        self._chk(self._lib.pmhip_scene_set_conf(self._h, idx, c))
 
     def view_size(self, idx):
         """(w, h) of a view's maps: the scene's, or the view's own (scene_set_view_sized)."""
         _, w, h = self._scene
-        return getattr(self, "_sizes", {}).get(int(idx), (w, h))
+        return self._sizes.get(int(idx), (w, h))
 
     def scene_get_maps(self, idx):
         w, h = self.view_size(idx)
         d = np.zeros((h, w), np.float32); n = np.zeros((h, w, 3), np.float32); c = np.zeros((h, w), np.float32)
-        self._chk(self._lib.pmhip_scene_get_maps(self._h, idx, _fp(d), _fp(n), _fp(c)))
+        self._chk(self._lib.pmhip_scene_get_maps(self._h, idx, d, n, c))
         return d, n, c
 
     def scene_device_ptr(self, what, idx=0) -> int:
@@ -406,18 +375,17 @@ class PatchMatchHIP:
     def scene_filter(self, view_ids, bAdjust=True, nMinViewsFilter=2, nMinViewsFilterAdjust=1, fDepthDiffThreshold=0.01, commit=True):
         """DepthMapsData::FilterDepthMap for these views (Scene::DenseReconstructionFilter); commit installs the results."""
         ids = np.ascontiguousarray(view_ids, np.int32)
-        self._chk(self._lib.pmhip_scene_filter(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), 1 if bAdjust else 0,
-                                               C.c_uint32(nMinViewsFilter), C.c_uint32(nMinViewsFilterAdjust), C.c_float(fDepthDiffThreshold), 1))
+        self._chk(self._lib.pmhip_scene_filter(self._h, ids, len(ids), bool(bAdjust), nMinViewsFilter, nMinViewsFilterAdjust, fDepthDiffThreshold, True))
         if commit:
             self._chk(self._lib.pmhip_scene_filter_commit(self._h))
 
     def scene_remove_small_segments(self, view_ids, nSpeckleSize=100, fDepthDiffThreshold=0.01):
         ids = np.ascontiguousarray(view_ids, np.int32)
-        self._chk(self._lib.pmhip_scene_remove_small_segments(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.c_uint32(nSpeckleSize), C.c_float(fDepthDiffThreshold)))
+        self._chk(self._lib.pmhip_scene_remove_small_segments(self._h, ids, len(ids), nSpeckleSize, fDepthDiffThreshold))
 
     def scene_gap_interpolation(self, view_ids, nIpolGapSize=7, fDepthDiffThreshold=0.01):
         ids = np.ascontiguousarray(view_ids, np.int32)
-        self._chk(self._lib.pmhip_scene_gap_interpolation(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.c_uint32(nIpolGapSize), C.c_float(fDepthDiffThreshold)))
+        self._chk(self._lib.pmhip_scene_gap_interpolation(self._h, ids, len(ids), nIpolGapSize, fDepthDiffThreshold))
 
     def scene_set_color(self, idx, bgr):
         """8-bit BGR image of a view at depth-map resolution (only fusion with bEstimateColor reads it)."""
@@ -425,23 +393,21 @@ class PatchMatchHIP:
         w, h = self.view_size(idx)
         if b.shape != (h, w, 3):
             raise ValueError("bgr must be (h, w, 3) uint8")
-        self._chk(self._lib.pmhip_scene_set_color(self._h, idx, b.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._chk(self._lib.pmhip_scene_set_color(self._h, idx, b))
 
     def scene_fuse(self, order, nMinViewsFuse=2, fDepthDiffThreshold=0.01, fNormalDiffThreshold=25.0, bEstimateColor=True, bEstimateNormal=True):
         """DepthMapsData::FuseDepthMaps over the resident maps (libs/MVS/SceneDensify.cpp:1372-1650); `order` = views, best connected
         first.  Returns a dict with the fields of MVS::PointCloud: points, viewStart/views/weights (CSR), projs, colors (BGR), normals."""
         od = np.ascontiguousarray(order, np.int32)
-        prm = PMHipFuseParams(nMinViewsFuse, fDepthDiffThreshold, fNormalDiffThreshold, 1 if bEstimateColor else 0, 1 if bEstimateNormal else 0)
+        prm = PMHipFuseParams(nMinViewsFuse, fDepthDiffThreshold, fNormalDiffThreshold, bool(bEstimateColor), bool(bEstimateNormal))
         nP, nV, nD = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._chk(self._lib.pmhip_scene_fuse(self._h, od.ctypes.data_as(C.POINTER(C.c_int32)), len(od), C.byref(prm), C.byref(nP), C.byref(nV), C.byref(nD)))
+        self._chk(self._lib.pmhip_scene_fuse(self._h, od, len(od), C.byref(prm), C.byref(nP), C.byref(nV), C.byref(nD)))
         P, V = int(nP.value), int(nV.value)
         pts = np.zeros((P, 3), np.float32); vs = np.zeros(P + 1, np.uint32); views = np.zeros(V, np.uint32); wts = np.zeros(V, np.float32)
         projs = np.zeros((V, 2), np.uint16)
         cols = np.zeros((P, 3), np.uint8) if bEstimateColor else None
         nrm = np.zeros((P, 3), np.float32) if bEstimateNormal else None
-        vp = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))
-        self._chk(self._lib.pmhip_scene_fuse_get(self._h, vp(pts, C.c_float), vp(vs, C.c_uint32), vp(views, C.c_uint32), vp(wts, C.c_float),
-                                                 vp(projs, C.c_uint16), vp(cols, C.c_uint8), vp(nrm, C.c_float)))
+        self._chk(self._lib.pmhip_scene_fuse_get(self._h, pts, vs, views, wts, projs, cols, nrm))
         return dict(nPoints=P, nDepths=int(nD.value), points=pts, viewStart=vs, views=views, weights=wts, projs=projs, colors=cols, normals=nrm,
                     rounds=int(self._lib.pmhip_scene_fuse_rounds(self._h)))
 
@@ -453,12 +419,11 @@ class PatchMatchHIP:
         P, V = int(nP.value), int(nV.value)
         pts = np.zeros((P, 3), np.float32); vs = np.zeros(P + 1, np.uint32); views = np.zeros(V, np.uint32); wts = np.zeros(V, np.float32)
         projs = np.zeros((V, 2), np.uint16)
-        vp = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))
-        self._chk(self._lib.pmhip_scene_fuse_get(self._h, vp(pts, C.c_float), vp(vs, C.c_uint32), vp(views, C.c_uint32), vp(wts, C.c_float), vp(projs, C.c_uint16), None, None))
+        self._chk(self._lib.pmhip_scene_fuse_get(self._h, pts, vs, views, wts, projs, None, None))
         cols = np.zeros((P, 3), np.uint8); nrm = np.zeros((P, 3), np.float32)
-        if self._lib.pmhip_scene_fuse_get(self._h, None, None, None, None, None, vp(cols, C.c_uint8), None) != 0:
+        if self._lib.pmhip_scene_fuse_get(self._h, None, None, None, None, None, cols, None) != 0:
             cols = None
-        if self._lib.pmhip_scene_fuse_get(self._h, None, None, None, None, None, None, vp(nrm, C.c_float)) != 0:
+        if self._lib.pmhip_scene_fuse_get(self._h, None, None, None, None, None, None, nrm) != 0:
             nrm = None
         return dict(nPoints=P, points=pts, viewStart=vs, views=views, weights=wts, projs=projs, colors=cols, normals=nrm)
 
@@ -474,8 +439,8 @@ class PatchMatchHIP:
             prm.obbPos[:] = [float(v) for v in np.asarray(pos, np.float32).ravel()]
             prm.obbExt[:] = [float(v) for v in np.asarray(ext, np.float32).ravel()]
         prm.fBorderROI = float(border_roi)
-        prm.bEstimateColor = 1 if estimate_colors else 0
-        prm.bEstimateNormal = 1 if estimate_normals else 0
+        prm.bEstimateColor = bool(estimate_colors)
+        prm.bEstimateNormal = bool(estimate_normals)
         prm.nNeighbors = int(n_neighbors)
         self._chk(self._lib.pmhip_scene_cloud_finish(self._h, C.byref(prm), None, None))
         t = (C.c_double * 4)()
@@ -491,8 +456,7 @@ class PatchMatchHIP:
         w = None if weights is None else np.ascontiguousarray(weights, np.float32)
         if len(vs) != len(pts) + 1:
             raise ValueError("viewStart must have nPoints + 1 entries")
-        self._chk(self._lib.pmhip_scene_cloud_set(self._h, _fp(pts), vs.ctypes.data_as(C.POINTER(C.c_uint32)), vv.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  None if w is None else _fp(w), C.c_uint64(len(pts))))
+        self._chk(self._lib.pmhip_scene_cloud_set(self._h, pts, vs, vv, w, len(pts)))
 
     def scene_cloud_load(self, points, viewStart, views, weights=None, colors=None, normals=None, n_cams=0):
         """Replace the resident cloud, colours (BGR bytes) and normals included when given (pmhip_scene_cloud_load).  `n_cams` > 0: the number of cameras the
@@ -506,9 +470,7 @@ class PatchMatchHIP:
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
         if (w is not None and len(w) != len(vv)) or (col is not None and len(col) != len(pts)) or (nrm is not None and len(nrm) != len(pts)):
             raise ValueError("weights go with the views, colours and normals with the points")
-        self._chk(self._lib.pmhip_scene_cloud_load(self._h, _fp(pts), vs.ctypes.data_as(C.POINTER(C.c_uint32)), vv.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                   None if w is None else _fp(w), None if col is None else col.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                   None if nrm is None else _fp(nrm), C.c_uint64(len(pts)), C.c_int32(int(n_cams))))
+        self._chk(self._lib.pmhip_scene_cloud_load(self._h, pts, vs, vv, w, col, nrm, len(pts), n_cams))
 
     def scene_cloud_filter(self, th_remove=None, min_views=0, cam_C=None, cam_angle=None):
         """Scene::PointCloudFilter(th_remove) (--filter-point-cloud) on the resident cloud, after PointCloud::RemoveMinViews(min_views) when `min_views` > 0
@@ -528,8 +490,8 @@ class PatchMatchHIP:
             if len(cc) != len(ca):
                 raise ValueError("cam_C and cam_angle must have one entry per camera")
             keep = (cc, ca)
-            prm.nCams = len(ca); prm.camC = cc.ctypes.data_as(C.POINTER(C.c_double)); prm.camAngle = _fp(ca)
-        n_cams = prm.nCams if cam_C is not None else getattr(self, "_scene", (0,))[0]
+            prm.nCams = len(ca); prm.camC = cc.ctypes.data_as(C.POINTER(C.c_double)); prm.camAngle = ca.ctypes.data_as(C.POINTER(C.c_float))
+        n_cams = prm.nCams if cam_C is not None else (self._scene or (0,))[0]
         # two calls when both are asked for: the size of the cloud between them is the size of `visibility`
         before = C.c_uint64(); t = (C.c_double * 3)(); t_min = 0.0
         if prm.nMinViews and prm.bVisibility:
@@ -549,9 +511,9 @@ class PatchMatchHIP:
         out["visibility"] = None; out["cones"] = None
         if th_remove is not None and int(before.value) > 0:
             cones = np.zeros((n_cams, 2), np.float32)
-            self._chk(self._lib.pmhip_scene_cloud_filter_cones(self._h, _fp(cones)))
+            self._chk(self._lib.pmhip_scene_cloud_filter_cones(self._h, cones))
             vis = np.zeros(int(before.value), np.int32)
-            self._chk(self._lib.pmhip_scene_cloud_visibility(self._h, vis.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(len(vis))))
+            self._chk(self._lib.pmhip_scene_cloud_visibility(self._h, vis, len(vis)))
             out["cones"] = cones; out["visibility"] = vis
         return out
 
@@ -559,32 +521,31 @@ class PatchMatchHIP:
         """The k nearest points of the resident cloud for each query index, nearest first (pmhip_scene_cloud_knn): (nq, k) uint32."""
         q = np.ascontiguousarray(queries, np.uint32)
         out = np.zeros((len(q), int(k)), np.uint32)
-        self._chk(self._lib.pmhip_scene_cloud_knn(self._h, int(k), q.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint32(len(q)), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._chk(self._lib.pmhip_scene_cloud_knn(self._h, k, q, len(q), out))
         return out
 
     def scene_copy(self, what, first, count, device_ptr, to_engine):
-        self._chk(self._lib.pmhip_scene_copy(self._h, what, first, count, C.c_void_p(device_ptr), 1 if to_engine else 0))
+        self._chk(self._lib.pmhip_scene_copy(self._h, what, first, count, device_ptr, bool(to_engine)))
 
     def scene_images_updated(self):
         self._chk(self._lib.pmhip_scene_images_updated(self._h))
 
     def scene_maps_updated(self, first, count):
         """Depth maps of these views were written through scene_device_ptr(1, ...): see include/pmhip.h."""
-        self._chk(self._lib.pmhip_scene_maps_updated(self._h, int(first), int(count)))
+        self._chk(self._lib.pmhip_scene_maps_updated(self._h, first, count))
 
     def sync(self):
         self._chk(self._lib.pmhip_sync(self._h))
 
     def scene_bytes(self) -> int:
         """Device memory the resident scene holds right now (pmhip_scene_bytes)."""
-        self._lib.pmhip_scene_bytes.restype = C.c_uint64
         return int(self._lib.pmhip_scene_bytes(self._h))
 
     def stream(self) -> int:
         return int(self._lib.pmhip_stream(self._h) or 0)
 
     def stats_reset(self, enable=True):
-        self._chk(self._lib.pmhip_stats_reset(self._h, 1 if enable else 0))
+        self._chk(self._lib.pmhip_stats_reset(self._h, bool(enable)))
 
     def stats_get(self) -> PMHipKernelStats:
         s = PMHipKernelStats()
@@ -593,20 +554,20 @@ class PatchMatchHIP:
 
     def prof_get(self, reset=True):
         out = (C.c_ulonglong * 16)()
-        self._chk(self._lib.pmhip_prof_get(self._h, out, 1 if reset else 0))
+        self._chk(self._lib.pmhip_prof_get(self._h, out, bool(reset)))
         return list(out)
 
     # -- self-test hooks -----------------------------------------------------------------------
     def math_eval(self, kind, a, b=None):
         a = np.ascontiguousarray(a, np.float32); b = a if b is None else np.ascontiguousarray(b, np.float32)
         o = np.zeros_like(a)
-        self._chk(self._lib.pmhip_math_eval(self._h, kind, _fp(a), _fp(b), _fp(o), C.c_size_t(a.size)))
+        self._chk(self._lib.pmhip_math_eval(self._h, kind, a, b, o, a.size))
         return o
 
     def resize(self, kind, img, arg=2):
         img = np.ascontiguousarray(img, np.float32); h, w = img.shape
         o = np.zeros((int(np.rint(h / arg)), int(np.rint(w / arg))) if kind == 0 else (h * 2, w * 2), np.float32)
-        self._chk(self._lib.pmhip_resize(self._h, kind, _fp(img), w, h, arg, _fp(o)))
+        self._chk(self._lib.pmhip_resize(self._h, kind, img, w, h, arg, o))
         return o
 
     RESAMPLE_AREA, RESAMPLE_UPSAMPLE, RESAMPLE_NEAREST_DOWN, RESAMPLE_NEAREST_UP, RESAMPLE_MASK_LEVEL, RESAMPLE_SKEW, RESAMPLE_QUAD = range(7)
@@ -626,8 +587,7 @@ class PatchMatchHIP:
         src = np.ascontiguousarray(src, dt)
         if src.size != ns:
             raise ValueError("resample: src must hold %d elements" % ns)
-        self._chk(self._lib.pmhip_resample(self._h, C.c_int(int(kind)), src.ctypes.data_as(C.c_void_p), C.c_int(sw), C.c_int(sh), dst.ctypes.data_as(C.c_void_p),
-                                           C.c_int(dw), C.c_int(dh), C.c_int(int(arg)), C.c_int(int(n_img))))
+        self._chk(self._lib.pmhip_resample(self._h, kind, src, sw, sh, dst, dw, dh, arg, n_img))
         return dst
 
     def close(self):
