@@ -10,6 +10,7 @@
 //   :1884-1886,1919-1920 + :2069-2093  nOptimize: REMOVE_SPECKLES, FILL_GAPS             -> PostFilter()
 //   :1955-1980 / :2136-2222  ADJUST_FILTER: DenseReconstructionFilter                    -> FilterDepthMaps()
 //   :1695-1712 / :1372-1650  FuseDepthMaps (or MergeDepthMaps when nMinViewsFuse < 2)    -> FuseDepthMaps()
+//   :411-414    a .dmap stored without normals: EstimateNormalMap from its depths         -> SetDepthMap(); EstimateMissingNormals()
 //   DepthData::Save (DepthMap.cpp:234-252)                                                -> SaveDepthMaps() through include/dmapio.h
 //
 // Needs nothing of OpenMVS / OpenCV: views are described by plain pointers (an OpenMVS caller fills them from MVS::Image / DepthData,
@@ -108,6 +109,7 @@ public:
 		(void)anyMask;
 		ids_.resize((size_t)n);
 		for (int i = 0; i < n; ++i) ids_[(size_t)i] = i;
+		noNormals_.clear();
 	}
 
 	// The size Image::ResizeImage brings a W0 x H0 image to under OPTDENSE::nResolutionLevel / nMinResolution / nMaxResolution (pmhip_working_size): View::w, View::h of
@@ -228,6 +230,24 @@ public:
 		                         color ? pc.colors.data() : nullptr, normal ? pc.normals.data() : nullptr));
 	}
 
+	// A depth map that enters from outside instead of being estimated (a depthNNNN.dmap of an importer or a depth sensor, read with include/dmapio.h): depth and
+	// confidence (may be null) become the view's resident maps, ViewWidth(idx) x ViewHeight(idx) entries.  normal == null: the map was stored without normals, and
+	// EstimateMissingNormals() makes them from the depths, as DepthMapsData::InitViews does (EstimateNormalMap, SceneDensify.cpp:411-414).
+	void SetDepthMap(int idx, const float* depth, const float* normal, const float* conf) {
+		if (!depth) throw std::runtime_error("DenseDepthMapsHIP: SetDepthMap without a depth map");
+		check(pmhip_scene_set_maps(e_, idx, depth, normal));
+		if (conf) check(pmhip_scene_set_conf(e_, idx, conf));
+		noNormals_.erase(std::remove(noNormals_.begin(), noNormals_.end(), (int32_t)idx), noNormals_.end());
+		if (!normal) noNormals_.push_back((int32_t)idx);
+	}
+	// MVS::EstimateNormalMap on the device (pmhip_scene_estimate_normals) for the views SetDepthMap installed without normals since the last call; returns how many
+	size_t EstimateMissingNormals() {
+		const size_t n = noNormals_.size();
+		check(pmhip_scene_estimate_normals(e_, noNormals_.data(), (int)n));
+		noNormals_.clear();
+		return n;
+	}
+
 	// One view's maps back to the host (any pointer may be null); ViewWidth(idx) x ViewHeight(idx) entries
 	void GetMaps(int idx, float* depth, float* normal, float* conf) { check(pmhip_scene_get_maps(e_, idx, depth, normal, conf)); }
 	int ViewWidth(int idx) const { return views_[(size_t)idx].w > 0 ? views_[(size_t)idx].w : w_; }
@@ -267,6 +287,7 @@ private:
 	Options opt_;
 	std::vector<View> views_;
 	std::vector<int32_t> ids_;
+	std::vector<int32_t> noNormals_;   // views whose maps SetDepthMap installed without normals
 };
 
 } // namespace MVS

@@ -174,6 +174,7 @@ int pmhip_scene_remove_small_segments(pmhip_engine* e, const int32_t* viewIds, i
 /* DepthMapsData::GapInterpolation (SceneDensify.cpp:904-1045; OPTDENSE::nIpolGapSize 7, fDepthDiffThreshold 0.01): fills row then
  * column gaps of the depth / normal / confidence maps of these views, in place on the device. */
 int pmhip_scene_gap_interpolation(pmhip_engine* e, const int32_t* viewIds, int nViews, uint32_t nIpolGapSize, float fDepthDiffThreshold);
+/* MVS::EstimateNormalMap on the resident depth maps and on host buffers: include/pmhip_normals.h, included at the end of this header. */
 /* DepthMapsData::FuseDepthMaps (SceneDensify.cpp:1372-1650) over the resident depth / normal / confidence maps: every unclaimed depth
  * seeds a 3D point, claims the agreeing pixels of the view's neighbours (depth within fDepthDiffThreshold, normals within
  * fNormalDiffThreshold degrees), is kept if it gathered nMinViewsFuse views and then zeroes the neighbour depths it occludes.
@@ -371,4 +372,5 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #ifdef __cplusplus
 }
 #endif
+#include "pmhip_normals.h"
 #endif /* PMHIP_H_ */

@@ -13,6 +13,7 @@
 #include "pm_cloud.hip"
 #include "pm_cloud_filter.hip"
 #include "pm_image.hip"
+#include "pm_normal.hip"
 #include "hip_buf.h"
 #include <limits.h>
 #include <math.h>
@@ -837,3 +838,4 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #include "pm_host_fuse.hip"
 #include "pm_host_cloud.hip"
 #include "pm_host_image.hip"
+#include "pm_host_normal.hip"

@@ -62,10 +62,15 @@ def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_a
             if f["depth_map"].shape != want or f.get("confidence_map") is None:
                 raise ValueError("%s does not hold the maps of view %d (%s, expected %s with a confidence map)" % (done, v, f["depth_map"].shape, want))
             normal = f.get("normal_map")
-            if normal is None:                                     # a depth map stored without normals gets them from its depths (EstimateNormalMap, SceneDensify.cpp:411-414)
+            # a depth map stored without normals gets them from its depths (EstimateNormalMap, SceneDensify.cpp:411-414): on the device when the engine's class has
+            # the method (a stand-in that answers every name through __getattr__ does not), else on the host -- the same bits
+            on_device = normal is None and callable(getattr(type(engine), "scene_estimate_normals", None))
+            if normal is None and not on_device:
                 from . import views as _views
                 normal = _views.estimate_normal_map(scene.K[v], f["depth_map"])
             engine.scene_set_maps(v, f["depth_map"], normal)
+            if on_device:
+                engine.scene_estimate_normals([v])
             engine.scene_set_conf(v, f["confidence_map"])
             resumed.append(v)
         elif init_depth is not None and v in init_depth:

@@ -75,6 +75,8 @@ class PMHipTuning(C.Structure):
 _TYPES = {c.__name__: c for c in (PMHipParams, PMHipView, PMHipDepthData, PMHipKernelStats, PMHipFuseParams, PMHipCloudParams, PMHipCloudFilterParams, PMHipImageStats, PMHipTuning)}
 _SIGNATURES = _cabi.signatures("pmhip.h", _TYPES)
 EXPORTS = list(_SIGNATURES)          # every function include/pmhip.h declares
+_NORMALS_SIGNATURES = _cabi.signatures("pmhip_normals.h", _TYPES)          # ... and its companion header, which pmhip.h includes
+NORMALS_EXPORTS = list(_NORMALS_SIGNATURES)
 
 _LIB = None
 
@@ -92,6 +94,7 @@ def load_library() -> C.CDLL:
             raise RuntimeError("%s is a CPU-emulated test build, not a device library: refusing to load it outside the test-suite" % path)
         experiment = bool(os.environ.get("PMHIP_LIB"))        # (an older build of the library in an A/B run may lack some entry points; otherwise a missing one raises)
         _cabi.declare(lib, _SIGNATURES, allow_missing=experiment)
+        _cabi.declare(lib, _NORMALS_SIGNATURES, allow_missing=experiment)
         if hasattr(lib, "pmhip_abi_version") and lib.pmhip_abi_version() != PMHIP_ABI_VERSION and not experiment:
             raise RuntimeError("%s has struct layout version %d, these bindings are written for %d (include/pmhip.h)" % (path, lib.pmhip_abi_version(), PMHIP_ABI_VERSION))
         _LIB = lib
@@ -386,6 +389,21 @@ class PatchMatchHIP:
     def scene_gap_interpolation(self, view_ids, nIpolGapSize=7, fDepthDiffThreshold=0.01):
         ids = np.ascontiguousarray(view_ids, np.int32)
         self._chk(self._lib.pmhip_scene_gap_interpolation(self._h, ids, len(ids), nIpolGapSize, fDepthDiffThreshold))
+
+    def scene_estimate_normals(self, view_ids):
+        """MVS::EstimateNormalMap on the device for these views (pmhip_scene_estimate_normals): each one's resident normal map becomes
+        `views.estimate_normal_map(K, resident depth)`, bit for bit; depth and confidence stay.  Asynchronous on the engine stream."""
+        ids = np.ascontiguousarray(view_ids, np.int32).ravel()
+        self._chk(self._lib.pmhip_scene_estimate_normals(self._h, ids, len(ids)))
+
+    def estimate_normal_map(self, K, depth):
+        """`views.estimate_normal_map(K, depth)` on the device, host arrays in and out (pmhip_estimate_normal_map); needs no scene."""
+        d = np.ascontiguousarray(depth, np.float32)
+        if d.ndim != 2:
+            raise ValueError("depth must be (h, w)")
+        n = np.zeros(d.shape + (3,), np.float32)
+        self._chk(self._lib.pmhip_estimate_normal_map(self._h, np.ascontiguousarray(K, np.float64).reshape(9), d, d.shape[1], d.shape[0], n))
+        return n
 
     def scene_set_color(self, idx, bgr):
         """8-bit BGR image of a view at depth-map resolution (only fusion with bEstimateColor reads it)."""

@@ -209,32 +209,39 @@ def match_scene(be, sc, cams, bgr, neighbors, out_dir, n_views=0, f_min_score_ra
     return done
 
 
+def _fuse_image(be, cams, sizes, neighbors, pair_dir, i, n_views=0, f_min_score_ratio=0.03, f_min_score=2.0, min_views=2):
+    """`SemiGlobalMatcher::Fuse` for image i: (depth, conf), or None when none of its listed pairs has a disparity file."""
+    import os
+    from . import dmap
+    cam = lambda i: (cams.K[i], cams.R[i], cams.C[i])
+    pairs = []
+    for j in _listed(neighbors[i], n_views, f_min_score_ratio, f_min_score):
+        direct, swapped = os.path.join(pair_dir, pair_file_name(i, j)), os.path.join(pair_dir, pair_file_name(j, i))
+        if os.path.exists(direct):
+            g = dmap.load_dimap(direct)
+        elif os.path.exists(swapped):
+            g = dmap.load_dimap(swapped)
+            g["Q"] = swapped_pair_q(g["Q"], cam(i), cam(j))
+        else:
+            continue                                         # "no disparity-data file found for image pair"
+        pairs.append(dict(disparity=g["disparity"], cost=g["cost"], Q=g["Q"], subpixel_steps=g["subpixel_steps"], image_size=tuple(sizes[i])))
+    return fuse_pairs(be, pairs, min_views) if pairs else None
+
+
 def fuse_scene(be, cams, sizes, neighbors, pair_dir, n_views=0, f_min_score_ratio=0.03, f_min_score=2.0, min_views=2, estimate_normals=True):
     """`SemiGlobalMatcher::Fuse` for every image (DenseReconstruction with nFusionMode == -2, SceneDensify.cpp:2049-2057): the disparity files of the image's listed
     neighbours -- stored as (image, neighbour), or as (neighbour, image) with Q carried over (`swapped_pair_q`) -- projected into the image and fused per pixel; normals from
     the depths (`views.estimate_normal_map`) when `estimate_normals` (nEstimateNormals == 2).  sizes: {image: (w, h)}.
     Returns {image: (depth, normal or None, conf)}; the depth range of such a map is (ZEROTOLERANCE, FLT_MAX), :2056."""
-    import os
-    from . import dmap, views
-    cam = lambda i: (cams.K[i], cams.R[i], cams.C[i])
+    from . import views
     out = {}
     for i in sorted(neighbors):
-        pairs = []
-        for j in _listed(neighbors[i], n_views, f_min_score_ratio, f_min_score):
-            direct, swapped = os.path.join(pair_dir, pair_file_name(i, j)), os.path.join(pair_dir, pair_file_name(j, i))
-            if os.path.exists(direct):
-                g = dmap.load_dimap(direct)
-            elif os.path.exists(swapped):
-                g = dmap.load_dimap(swapped)
-                g["Q"] = swapped_pair_q(g["Q"], cam(i), cam(j))
-            else:
-                continue                                         # "no disparity-data file found for image pair"
-            pairs.append(dict(disparity=g["disparity"], cost=g["cost"], Q=g["Q"], subpixel_steps=g["subpixel_steps"], image_size=tuple(sizes[i])))
-        if not pairs:
+        fused = _fuse_image(be, cams, sizes, neighbors, pair_dir, i, n_views, f_min_score_ratio, f_min_score, min_views)
+        if fused is None:
             w, h = sizes[i]
             out[i] = (np.zeros((h, w), np.float32), None, np.zeros((h, w), np.float32))
             continue
-        depth, conf = fuse_pairs(be, pairs, min_views)
+        depth, conf = fused
         out[i] = (depth, views.estimate_normal_map(cams.K[i], depth) if estimate_normals else None, conf)
     return out
 
@@ -255,17 +262,66 @@ class DeviceBackend:
         return getattr(self.m, name)
 
 
-def dense_reconstruction(be, mvs_in, out_dir, fusion_mode, opt=None, image_loader=None, min_resolution=320):
+def to_the_cloud(be, sv, cams, sizes, neighbors, out_dir, opt, mvs_in, mvs_out, crop_to_roi=False, border_roi=0.0, **listing):
+    """What `Scene::ComputeDepthMaps` and `DenseReconstruction` do in mode -2 after `SemiGlobalMatcher::Fuse` (SceneDensify.cpp:2053-2117, :1955, :1690-1737), on the
+    backend's PatchMatch engine `be.e`, loaded here with the scene `sv` (`densify.load_scene`).  Per image, in order: Fuse (`fuse_pairs`; an image without a pair file holds
+    all-zero maps), depth and confidence installed in the resident scene with the range (ZEROTOLERANCE, FLT_MAX) of :2056, EstimateNormalMap on the device
+    (`scene_estimate_normals`), RemoveSmallSegments and GapInterpolation per nOptimize, `depthNNNN.dmap` written from the resident maps.  Then the cross-view filter (nOptimize
+    & ADJUST_FILTER; the filtered maps are written again), FuseDepthMaps, the crop / colours / normals block and the dense archive at `mvs_out`, with the arguments
+    `densify.dense_reconstruction` derives from `opt`.  Depth and confidence travel through the host between the two libraries.  Returns the cloud."""
+    from . import densify, mvsi
+    engine = be.e
+    n_optimize, th = int(opt.nOptimize), float(opt.fDepthDiffThreshold)
+    engine.scene_load(sv, n_levels=int(opt.nSubResolutionLevels))
+    ids = sorted(neighbors)
+    d_min, d_max = 1e-4, float(np.finfo(np.float32).max)              # ZEROTOLERANCE<float>() = FZERO_TOLERANCE (libs/Common/Types.h:579), FLT_MAX
+    for i in ids:
+        fused = _fuse_image(be, cams, sizes, neighbors, out_dir, i, min_views=2, **listing)
+        w, h = sizes[i]
+        depth, conf = fused if fused is not None else (np.zeros((h, w), np.float32), np.zeros((h, w), np.float32))
+        sv.dmin[i], sv.dmax[i] = d_min, d_max
+        engine.scene_set_view(i, None, sv.K[i], sv.R[i], sv.C[i], d_min, d_max, sv.neighbors[i])      # the image neighbours, as the filter and the fusion read them
+        engine.scene_set_maps(i, depth, None)
+        engine.scene_set_conf(i, conf)
+        engine.scene_estimate_normals([i])
+        if n_optimize & densify.REMOVE_SPECKLES:
+            engine.scene_remove_small_segments([i], int(opt.nSpeckleSize), th)
+        if n_optimize & densify.FILL_GAPS:
+            engine.scene_gap_interpolation([i], int(opt.nIpolGapSize), th)
+        densify.save_depth_maps(engine, sv, [i], out_dir, sv.names)
+    if n_optimize & densify.ADJUST_FILTER and ids:
+        engine.scene_filter(ids, bool(opt.bFilterAdjust), int(opt.nMinViewsFilter), int(opt.nMinViewsFilterAdjust), th, commit=True)
+        densify.save_depth_maps(engine, sv, ids, out_dir, sv.names)
+    cloud = densify.fuse_depth_maps(engine, sv, opt, bgr=sv.bgr)
+    cloud = densify.finish_point_cloud(engine, (sv, mvsi.load(mvs_in) if crop_to_roi else None), opt, crop_to_roi, border_roi, cloud=cloud)
+    densify.save_dense_scene(mvs_in, mvs_out, cloud, sv)
+    return cloud
+
+
+def dense_reconstruction(be, mvs_in, out_dir, fusion_mode, opt=None, image_loader=None, min_resolution=320, mvs_out=None, crop_to_roi=False, border_roi=0.0, seed=0):
     """The SGM modes of `Scene::DenseReconstruction` (libs/MVS/SceneDensify.cpp:1655-1750, :2042-2058): `fusion_mode` -1 writes the disparity files of every image's
     pairs into `out_dir`; -2 fuses the files found there into depth maps and writes `depthNNNN.dmap` (depth, normals when nEstimateNormals == 2, confidence; depth range
-    (ZEROTOLERANCE, FLT_MAX) as at :2056) -- what a later `--fusion-mode 0` run fuses into the cloud.  be: a backend (`DeviceBackend(SemiGlobalMatcherHIP(dev),
-    PatchMatchHIP(dev))`); opt: an `optdense.OptDense` (nNumViews, view-score cuts, resolution level); image_loader as in `densify.load_scene`.
-    Returns the pairs written (-1) or {image: (depth, normal, conf)} (-2)."""
+    (ZEROTOLERANCE, FLT_MAX) as at :2056).  be: a backend (`DeviceBackend(SemiGlobalMatcherHIP(dev), PatchMatchHIP(dev))`); opt: an `optdense.OptDense` (nNumViews,
+    view-score cuts, resolution level); image_loader as in `densify.load_scene`.
+    Without `mvs_out` mode -2 stops at the depth maps, which a later `--fusion-mode 0` run fuses into the cloud.  Returns the pairs written (-1) or
+    {image: (depth, normal, conf)} (-2).
+    `mvs_out` (mode -2 only): the reference's mode -2 through to the cloud (`to_the_cloud` below), the dense archive written there; `crop_to_roi` / `border_roi` as in
+    `densify.dense_reconstruction`, and `seed` for the same signature (nothing on this route draws a random number).  Returns the cloud dict of
+    `densify.dense_reconstruction`."""
     import os
     from . import densify, dmap, mvsi, optdense, views
     if fusion_mode not in (-1, -2):
         raise ValueError("the SGM path is fusion modes -1 and -2")
     opt = opt or optdense.defaults()
+    if mvs_out is not None:
+        if fusion_mode != -2:
+            raise ValueError("mvs_out: only fusion mode -2 goes on to the cloud (-1 writes the pairs' disparity files)")
+        if int(opt.nEstimateNormals) != 2:
+            # FuseDepthMaps(pointcloud, nEstimateColors == 2, nEstimateNormals == 2), SceneDensify.cpp:1443-1444,1553: without normal maps the reference fuses with a constant normal
+            raise ValueError("mvs_out with nEstimateNormals = %d: the reference then fuses the depth maps without normal maps (bNormalMap == false), "
+                             "a fusion mode this engine does not have; set nEstimateNormals = 2" % int(opt.nEstimateNormals))
+        if getattr(be, "e", None) is None:
+            raise ValueError("mvs_out needs the backend's PatchMatch engine (DeviceBackend.e): the filters and the fusion run there")
     sv = densify.load_scene(mvs_in, opt=opt, image_loader=image_loader)
     sc = mvsi.load(mvs_in)
     cams = views.Cameras(sc, sv.sizes[:len(sc.images)])          # every image at its own size; the slots behind them are PatchMatch's resampled neighbour copies
@@ -274,6 +330,8 @@ def dense_reconstruction(be, mvs_in, out_dir, fusion_mode, opt=None, image_loade
     if fusion_mode == -1:
         return match_scene(be, sc, cams, sv.bgr, nbs, out_dir, min_resolution=min_resolution, avg_depth=sv.avg_depth, **args)
     sizes = {i: tuple(sv.sizes[i]) for i in nbs}
+    if mvs_out is not None:
+        return to_the_cloud(be, sv, cams, sizes, nbs, out_dir, opt, mvs_in, mvs_out, crop_to_roi, border_roi, **args)
     fused = fuse_scene(be, cams, sizes, nbs, out_dir, min_views=2, estimate_normals=int(opt.nEstimateNormals) == 2, **args)
     for i, (depth, normal, conf) in fused.items():
         ids = [i] + [int(v) for v in sv.neighbors[i]]
