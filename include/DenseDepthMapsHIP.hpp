@@ -11,6 +11,7 @@
 //   :1955-1980 / :2136-2222  ADJUST_FILTER: DenseReconstructionFilter                    -> FilterDepthMaps()
 //   :1695-1712 / :1372-1650  FuseDepthMaps (or MergeDepthMaps when nMinViewsFuse < 2)    -> FuseDepthMaps()
 //   :411-414    a .dmap stored without normals: EstimateNormalMap from its depths         -> SetDepthMap(); EstimateMissingNormals()
+//   Mesh::Project (Mesh.cpp:3874-3968) of --mesh-file / --export-depth-maps-name          -> SetMesh(); ProjectMesh(); ReleaseMesh()
 //   DepthData::Save (DepthMap.cpp:234-252)                                                -> SaveDepthMaps() through include/dmapio.h
 //
 // Needs nothing of OpenMVS / OpenCV: views are described by plain pointers (an OpenMVS caller fills them from MVS::Image / DepthData,
@@ -247,6 +248,33 @@ public:
 		noNormals_.clear();
 		return n;
 	}
+
+	// A triangle mesh (Scene::mesh after --mesh-file) made resident for ProjectMesh: 3 floats per vertex, 3 vertex indices per face; vertexNormals null: computed as
+	// Mesh::ComputeNormalVertices does.  Independent of the loaded scene.
+	void SetMesh(const float* vertices, uint32_t nVertices, const uint32_t* faces, uint32_t nFaces, const float* vertexNormals = nullptr) {
+		check(pmhip_mesh_set(e_, vertices, nVertices, faces, nFaces, vertexNormals));
+	}
+	// Mesh::Project(camera, depthMap, normalMap) into the listed views of the loaded scene, each at its own size and camera, in one call (what
+	// Scene::ExportMeshToDepthMaps renders, Scene.cpp:680-736).  depth[k] receives ViewWidth x ViewHeight floats of view ids[k], normal[k] three times as many;
+	// withNormals = false: depth only, `normal` is left alone.
+	void ProjectMesh(const std::vector<int32_t>& ids, std::vector<std::vector<float>>& depth, std::vector<std::vector<float>>& normal, bool withNormals = true) {
+		const size_t n = ids.size();
+		std::vector<double> K(9 * n), R(9 * n), C(3 * n);
+		std::vector<int32_t> wh(2 * n);
+		std::vector<float*> dp(n), np(n);
+		depth.resize(n);
+		if (withNormals) normal.resize(n);
+		for (size_t k = 0; k < n; ++k) {
+			const View& v = views_.at((size_t)ids[k]);
+			std::memcpy(&K[9 * k], v.K, 72); std::memcpy(&R[9 * k], v.R, 72); std::memcpy(&C[3 * k], v.C, 24);
+			wh[2 * k] = ViewWidth(ids[k]); wh[2 * k + 1] = ViewHeight(ids[k]);
+			const size_t P = (size_t)wh[2 * k] * wh[2 * k + 1];
+			depth[k].assign(P, 0.f); dp[k] = depth[k].data();
+			if (withNormals) { normal[k].assign(3 * P, 0.f); np[k] = normal[k].data(); }
+		}
+		check(pmhip_mesh_project(e_, (int)n, K.data(), R.data(), C.data(), wh.data(), dp.data(), withNormals ? np.data() : nullptr));
+	}
+	void ReleaseMesh() { check(pmhip_mesh_release(e_)); }
 
 	// One view's maps back to the host (any pointer may be null); ViewWidth(idx) x ViewHeight(idx) entries
 	void GetMaps(int idx, float* depth, float* normal, float* conf) { check(pmhip_scene_get_maps(e_, idx, depth, normal, conf)); }

@@ -14,6 +14,7 @@
 #include "pm_cloud_filter.hip"
 #include "pm_image.hip"
 #include "pm_normal.hip"
+#include "pm_mesh.hip"
 #include "hip_buf.h"
 #include <limits.h>
 #include <math.h>
@@ -200,9 +201,29 @@ struct ImageStore {
 	PMHipImageStats stats{};
 };
 
+// The resident mesh (pm_host_mesh.hip) and the working buffers of its renders (grow only, freed with the mesh).  Independent of the scene, like the image store.
+#ifndef PM_MESH_BOX_PIXELS
+#define PM_MESH_BOX_PIXELS 64          // a face whose clipped box holds more pixels goes to the workgroup route (pmhip_mesh_set_tuning; chosen by tools/mesh_project_bench.py)
+#endif
+#ifndef PM_MESH_BATCH_BYTES
+#define PM_MESH_BATCH_BYTES (4ull << 30)   // device memory of one batch of views: vertex records, face lists, keys and maps
+#endif
+#define PM_MESH_MAX_BLOCKS 16384       // grid.x of the strided kernels
+#define PM_MESH_LARGE_BLOCKS 2048      // workgroups per view that share the listed faces
+struct MeshMem {
+	DevBuf<float> verts, normals; DevBuf<uint32_t> faces;
+	uint32_t nV = 0, nF = 0; bool set = false;
+	int boxMax = PM_MESH_BOX_PIXELS; uint64_t batchBytes = PM_MESH_BATCH_BYTES;
+	DevBuf<PMMeshView> views; DevBuf<PMMeshVert> rec; DevBuf<unsigned long long> keys; DevBuf<float> depth, normal;
+	DevBuf<uint32_t> largeCount, largeList, bits;
+	uint64_t statBatches = 0, statLarge = 0; double statMs = 0;
+	hipEvent_t ev[2] = {nullptr, nullptr};                   // bracket the clears and kernels of a batch (pmhip_mesh_get_stats)
+};
+
 struct pmhip_engine : SceneMem {
 	int device = 0;
 	ImageStore img;
+	MeshMem mesh;
 	hipEvent_t imgEv[2] = {nullptr, nullptr};     // bracket every kernel of the store (PMHipImageStats::kernelMs)
 	hipStream_t stream = nullptr;
 	// view groups of a batch sweep on their own streams so that the tail of one group's diagonal launch
@@ -253,6 +274,15 @@ static void freeImages(pmhip_engine* e) {
 	const PMHipImageStats kept = e->img.stats;
 	e->img = ImageStore{};
 	e->img.stats = kept;
+}
+
+// ... and the mesh with its working buffers (the tuning is the engine's and stays)
+static void freeMesh(pmhip_engine* e) {
+	hipSetDevice(e->device);
+	const int box = e->mesh.boxMax; const uint64_t bytes = e->mesh.batchBytes;
+	for (hipEvent_t ev : e->mesh.ev) if (ev) hipEventDestroy(ev);
+	e->mesh = MeshMem{};
+	e->mesh.boxMax = box; e->mesh.batchBytes = bytes;
 }
 
 #include "pm_host_estimate.hip"
@@ -306,6 +336,7 @@ void pmhip_destroy(pmhip_engine* e) {
 	for (auto& ev : e->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
 	freeScene(e);
 	freeImages(e);
+	freeMesh(e);
 	for (hipEvent_t ev : e->imgEv) if (ev) hipEventDestroy(ev);
 	for (int g = 0; g < 16; ++g) { if (e->gstream[g]) hipStreamDestroy(e->gstream[g]); if (e->joinEv[g]) hipEventDestroy(e->joinEv[g]); }
 	if (e->forkEv) hipEventDestroy(e->forkEv);
@@ -325,6 +356,7 @@ int pmhip_release(pmhip_engine* e) {
 	hipStreamSynchronize(e->stream);
 	freeScene(e);
 	freeImages(e);
+	freeMesh(e);
 	e->inited = false;
 	return 0;
 }
@@ -839,3 +871,4 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #include "pm_host_cloud.hip"
 #include "pm_host_image.hip"
 #include "pm_host_normal.hip"
+#include "pm_host_mesh.hip"

@@ -131,6 +131,7 @@ class SceneViews:
         self.bgr = []                               # the colour images at the working resolution (B, G, R), for the fused cloud's colours
         self.all_view_scores = {}                   # image -> its WHOLE scored neighbour list (Image::neighbors: fusion order, and what a dense archive stores)
         self.avg_depth = {}                         # image -> average depth of its sparse points (Image::avgDepth)
+        self.valid = []                             # per image: it has a pose (Image::IsValid); empty: all have
         self.stored = {}                            # slot -> key of the engine's image store that holds its images (load_scene(..., engine=...): `gray` / `bgr` are None there)
 
     @property
@@ -307,7 +308,8 @@ def scale_image(gray, scale):
     return _resize_cubic_f32(gray, w, h, 1.0 / s) if s > 1 else _resize_area_f32(gray, w, h, 1.0 / s)
 
 
-def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=None, ignore_mask_label=None, mask_path=None, mask_loader=None, engine=None):
+def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=None, ignore_mask_label=None, mask_path=None, mask_loader=None, engine=None,
+               mesh=None, mesh_engine=None):
     """Reads an MVSI scene and its images and runs view selection + depth initialisation for every valid image.
 
     `opt`: a `views.DenseOptions` or the whole option table (`optdense.OptDense`, e.g. from `optdense.load(<--dense-config-file>)`).
@@ -321,7 +323,11 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
     `engine` (a `PatchMatchHIP`): the images are prepared on the device.  Every decoded image goes straight to the engine's image store (`image_prepare`, key = its
     slot; one decoded image in host memory at a time), every resampled copy is made there (`image_scale`); `SceneViews.gray[i]` / `.bgr[i]` are None and
     `SceneViews.stored` = {slot: key} tells `PatchMatchHIP.scene_load` where the images are.  Sizes, view selection, seed maps and masks are the same (they never
-    read pixels), and so are the images, bit for bit.  Returns a `SceneViews`."""
+    read pixels), and so are the images, bit for bit.
+    `mesh` (`DensifyPointCloud --mesh-file`: a PLY file name, or (vertices, faces)): when no image of the scene carries neighbours, the sparse cloud is replaced by the
+    mesh's vertices with the images that see them (`views.sample_mesh_with_visibility`, Scene::ComputeDepthMaps, SceneDensify.cpp:1757-1760) before view selection;
+    with `mesh_engine` (a `PatchMatchHIP`) the renders and the visibility test run on the device (`mesh_visibility`) and the mesh is released afterwards.  A scene with
+    neighbours ignores the mesh, as there.  Returns a `SceneViews`."""
     import numpy as np
     from . import mvsi, views
     opt = opt or views.DenseOptions()
@@ -339,11 +345,12 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
             with Image.open(p) as im:
                 return np.asarray(im.convert("RGB"))
     sv = SceneViews()
-    rgbs, sizes = [], []
+    rgbs, sizes, decoded = [], [], []
     for im in sc.images:
         p = im.name if os.path.isabs(im.name) else os.path.join(base, im.name)
         rgb = image_loader(p)
         H, W = rgb.shape[:2]
+        decoded.append((W, H))
         res, _ = views.compute_max_resolution(W, H, opt.nResolutionLevel, opt.nMinResolution, opt.nMaxResolution)
         w, h = views.resized_size(W, H, res)
         if engine is not None:
@@ -371,11 +378,13 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
             except (OSError, ValueError):
                 continue                                                         # "warning: can not load the segmentation mask": the image is estimated unmasked
             sv.masks[i] = views.import_ignore_mask(labels, sizes[i], ignore_mask_label)
+    if mesh is not None and not any(len(im.view_scores) for im in sc.images):
+        replace_cloud_by_mesh(sc, mesh, decoded, mesh_engine)
     cams = views.Cameras(sc, sizes)
     for i, im in enumerate(sc.images):
         sv.gray.append(None if rgbs[i] is None else views.to_gray(rgbs[i])); sv.names.append(im.name)
         sv.bgr.append(None if rgbs[i] is None else np.ascontiguousarray(rgbs[i][..., ::-1]))
-        sv.K.append(cams.K[i]); sv.R.append(cams.R[i]); sv.C.append(cams.C[i])
+        sv.K.append(cams.K[i]); sv.R.append(cams.R[i]); sv.C.append(cams.C[i]); sv.valid.append(bool(im.is_valid()))
         whole = []
         sel = views.select_views(sc, cams, i, opt, all_neighbors=whole) if im.is_valid() else None
         if whole:
@@ -414,6 +423,72 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
             sv.estimate_neighbors[i][k] = made[key]
     assert len(sv.gray) == n_img + len(sv.alias_of)
     return sv
+
+
+def replace_cloud_by_mesh(sc, mesh, image_sizes, engine=None, max_resolution: int = 320):
+    """`Scene::SampleMeshWithVisibility` on an `mvsi.Scene`, in place: vertices and view lists become those of `views.sample_mesh_with_visibility`; normals, colours
+    and confidences of the cloud it replaces go (pointcloud.Release()).  `mesh`: a PLY file name or (vertices, faces); `image_sizes`: the images' own (width, height);
+    `engine`: a `PatchMatchHIP` that renders and tests on the device (the mesh is released afterwards), None: the host twin."""
+    import numpy as np
+    from . import meshio, mvsi, views
+    V, F = meshio.load_ply(mesh) if isinstance(mesh, (str, os.PathLike)) else mesh
+    sc.sizes = list(image_sizes)
+    vis = None
+    if engine is not None:
+        def vis(cams):
+            engine.mesh_set(V, F)
+            try:
+                return engine.mesh_visibility([c[0] for c in cams], [c[1] for c in cams], [c[2] for c in cams], [c[3:] for c in cams], len(V))
+            finally:
+                engine.mesh_release()
+    pts, start, ids = views.sample_mesh_with_visibility(sc, V, F, max_resolution, visibility=vis)
+    sc.vertices, sc.vertex_view_start = pts, start
+    sc.vertex_views = np.zeros(len(ids), mvsi.VIEW_DTYPE)
+    sc.vertex_views["image_id"] = ids
+    sc.vertices_normal = np.zeros((0, 3), np.float32); sc.vertices_color = np.zeros((0, 3), np.uint8)
+    return sc
+
+
+def export_mesh_depth_maps(scene, mesh, base_name: str, engine=None) -> list:
+    """`Scene::ExportMeshToDepthMaps(baseName)` (libs/MVS/Scene.cpp:680-736; `DensifyPointCloud --export-depth-maps-name` with `--mesh-file`): the mesh rendered into
+    every valid image at the working resolution -- `scene` is a `SceneViews` (`load_scene`), whose sizes and cameras come from the option table as there -- and one file
+    per image, named insertBeforeFileExt(base_name, "%04u" % ID).  `.dmap`: depth and normals (vertex normals as `Mesh::ComputeNormalVertices` makes them), IDs = the
+    image then its neighbours (`Image::neighbors`, the whole scored list), dMin 0.001, dMax FLT_MAX, no confidence; `.pfm`: depth only, as `TImage::Save` writes it
+    (little-endian, rows bottom to top).  Any other extension raises ValueError: the reference's colour-mapped PNG is not written.
+    `mesh`: a PLY file name or (vertices, faces); `engine`: a `PatchMatchHIP` that renders every image in one call (the mesh is released afterwards), None: the host
+    twin `views.project_mesh`.  Returns the file names."""
+    import numpy as np
+    from . import dmap, meshio, views
+    i = base_name.rfind(".")
+    ext = base_name[i:].lower() if i >= 0 else ""
+    if ext not in (".dmap", ".pfm"):
+        raise ValueError("export_mesh_depth_maps: extension '%s' of %s (.dmap: depth and normals, .pfm: depth)" % (ext, base_name))
+    V, F = meshio.load_ply(mesh) if isinstance(mesh, (str, os.PathLike)) else mesh
+    want_n = ext == ".dmap"
+    n_img = scene.n_views - len(getattr(scene, "alias_of", None) or {})
+    valid = getattr(scene, "valid", None) or [True] * n_img
+    ids = [v for v in range(n_img) if valid[v]]
+    if engine is not None:
+        engine.mesh_set(V, F)
+        try:
+            maps = engine.mesh_project([scene.K[v] for v in ids], [scene.R[v] for v in ids], [scene.C[v] for v in ids], [scene.sizes[v] for v in ids], normals=want_n)
+        finally:
+            engine.mesh_release()
+    else:
+        N = views.compute_normal_vertices(V, F) if want_n else None
+        maps = [views.project_mesh(scene.K[v], scene.R[v], scene.C[v], scene.sizes[v][0], scene.sizes[v][1], V, F, N) for v in ids]
+    out = []
+    for v, (depth, normal) in zip(ids, maps):
+        name = (base_name[:i] + "%04u" % v + base_name[i:]) if i >= 0 else base_name + "%04u" % v
+        if want_n:
+            nbs = scene.all_view_scores[v]["ID"] if v in (getattr(scene, "all_view_scores", None) or {}) else scene.neighbors[v]
+            dmap.save(name, scene.names[v], [v] + [int(k) for k in nbs], scene.sizes[v], scene.K[v], scene.R[v], scene.C[v], 0.001, float(np.finfo(np.float32).max), depth, normal)
+        else:
+            with open(name, "wb") as f:
+                f.write(("Pf\n%d %d\n%f\n" % (depth.shape[1], depth.shape[0], -1.0)).encode("ascii"))
+                f.write(np.ascontiguousarray(depth[::-1], "<f4").tobytes())
+        out.append(name)
+    return out
 
 
 # ---- the consumer of the depth maps: fusion and the dense scene archive ---------------------------------------------------------------------------
@@ -534,7 +609,8 @@ def filter_point_cloud(engine, mvs_in: str, mvs_out: str | None = None, th_remov
 
 
 def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None,
-                         crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, prepare_on_device: bool = False, **load_args):
+                         crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, prepare_on_device: bool = False, mesh_file: str | None = None,
+                         **load_args):
     """`Scene::DenseReconstruction(nFusionMode)` (libs/MVS/SceneDensify.cpp:1655-1750) for the PatchMatch path on one engine: prepare the views (`load_scene`), estimate all
     depth maps with the geometric rounds and the filters the option table asks for (`compute_depth_maps`; with `dmap_dir` under the reference's file contract), and -- unless
     `fusion_mode` is 1, "export depth maps only" -- fuse them and write `<scene>_dense.mvs` to `mvs_out`.  `opt`: an `optdense.OptDense` (default: the table's defaults with the
@@ -544,6 +620,7 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     `filter_point_cloud` < 0: `Scene::PointCloudFilter` with that threshold on the finished cloud (`PatchMatchHIP.scene_cloud_filter`; default 0: off).
     `prepare_on_device`: the decoded images are resized, converted and resampled on the engine (`load_scene(..., engine=engine)`) -- the same depth maps and cloud, but the
     returned `SceneViews` has no host images (`gray[i]` / `bgr[i]` are None), which is why it is off by default.
+    `mesh_file` (`--mesh-file`): a scene whose images carry no neighbours takes its sparse cloud from this mesh, rendered and tested on the engine (`load_scene(mesh=...)`).
     Returns (SceneViews, cloud or None)."""
     from . import optdense
     th_filter = int(filter_point_cloud)
@@ -551,6 +628,8 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
         raise ValueError("fusion_mode %d: the PatchMatch path is modes 0 (estimate + fuse) and 1 (depth maps only)" % fusion_mode)
     if opt is None:
         opt = optdense.defaults(); opt.nNumViews = 8; opt.nEstimateNormals = 2
+    if mesh_file is not None:
+        load_args = dict(load_args, mesh=mesh_file, mesh_engine=engine)
     sv = load_scene(mvs_in, opt=opt, engine=engine if prepare_on_device else None, **load_args)
     engine.scene_load(sv, n_levels=int(opt.nSubResolutionLevels))
     compute_depth_maps(engine, sv.ids, opt.params(seed), n_optimize=int(opt.nOptimize), b_filter_adjust=bool(opt.bFilterAdjust), n_speckle_size=int(opt.nSpeckleSize),

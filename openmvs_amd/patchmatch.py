@@ -77,6 +77,8 @@ _SIGNATURES = _cabi.signatures("pmhip.h", _TYPES)
 EXPORTS = list(_SIGNATURES)          # every function include/pmhip.h declares
 _NORMALS_SIGNATURES = _cabi.signatures("pmhip_normals.h", _TYPES)          # ... and its companion header, which pmhip.h includes
 NORMALS_EXPORTS = list(_NORMALS_SIGNATURES)
+_MESH_SIGNATURES = _cabi.signatures("pmhip_mesh.h", _TYPES)
+MESH_EXPORTS = list(_MESH_SIGNATURES)
 
 _LIB = None
 
@@ -95,6 +97,7 @@ def load_library() -> C.CDLL:
         experiment = bool(os.environ.get("PMHIP_LIB"))        # (an older build of the library in an A/B run may lack some entry points; otherwise a missing one raises)
         _cabi.declare(lib, _SIGNATURES, allow_missing=experiment)
         _cabi.declare(lib, _NORMALS_SIGNATURES, allow_missing=experiment)
+        _cabi.declare(lib, _MESH_SIGNATURES, allow_missing=experiment)
         if hasattr(lib, "pmhip_abi_version") and lib.pmhip_abi_version() != PMHIP_ABI_VERSION and not experiment:
             raise RuntimeError("%s has struct layout version %d, these bindings are written for %d (include/pmhip.h)" % (path, lib.pmhip_abi_version(), PMHIP_ABI_VERSION))
         _LIB = lib
@@ -404,6 +407,66 @@ class PatchMatchHIP:
         n = np.zeros(d.shape + (3,), np.float32)
         self._chk(self._lib.pmhip_estimate_normal_map(self._h, np.ascontiguousarray(K, np.float64).reshape(9), d, d.shape[1], d.shape[0], n))
         return n
+
+    # -- a mesh rendered into depth and normal maps (include/pmhip_mesh.h) ---------------------
+    def mesh_set(self, vertices, faces, vertex_normals=None):
+        """The mesh becomes resident (pmhip_mesh_set): vertices (n, 3) float32, faces (m, 3) vertex indices; `vertex_normals` (n, 3), or None: the engine computes them
+        as `views.compute_normal_vertices` does.  Returns the vertex normals in use."""
+        V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        F = np.asarray(faces).reshape(-1, 3)
+        if len(F) and (F.min() < 0 or F.max() > 0xFFFFFFFF):
+            raise ValueError("face indices must be vertex indices")
+        F = np.ascontiguousarray(F, np.uint32)
+        N = None if vertex_normals is None else np.ascontiguousarray(vertex_normals, np.float32).reshape(-1, 3)
+        if N is not None and N.shape != V.shape:
+            raise ValueError("one normal per vertex")
+        self._chk(self._lib.pmhip_mesh_set(self._h, V, len(V), F, len(F), N))
+        out = np.zeros_like(V)
+        self._chk(self._lib.pmhip_mesh_get_vertex_normals(self._h, out))
+        return out
+
+    @staticmethod
+    def _mesh_views(K, R, Cc, sizes):
+        K = np.ascontiguousarray(K, np.float64).reshape(-1, 9); R = np.ascontiguousarray(R, np.float64).reshape(-1, 9); Cc = np.ascontiguousarray(Cc, np.float64).reshape(-1, 3)
+        wh = np.ascontiguousarray(sizes, np.int32).reshape(-1, 2)
+        if not (len(K) == len(R) == len(Cc) == len(wh)):
+            raise ValueError("one K, R, C and (w, h) per view")
+        return K, R, Cc, wh
+
+    def mesh_project(self, K, R, Cc, sizes, normals=True):
+        """`views.project_mesh` of the resident mesh for many views in one call (pmhip_mesh_project): K, R (n, 3, 3), Cc (n, 3), sizes n x (w, h).  `normals`: a bool, or
+        one per view.  Returns [(depth (h, w), normal (h, w, 3) | None)] per view."""
+        K, R, Cc, wh = self._mesh_views(K, R, Cc, sizes)
+        n = len(wh)
+        want = [bool(normals)] * n if np.isscalar(normals) else [bool(v) for v in normals]
+        ok = bool((wh > 0).all())                 # (a refused size reaches the library, which says why; no array is made for it)
+        depth = [np.zeros((h, w) if ok else (1, 1), np.float32) for w, h in wh]
+        normal = [np.zeros((h, w, 3) if ok else (1, 1, 3), np.float32) if want[i] else None for i, (w, h) in enumerate(wh)]
+        fp = C.POINTER(C.c_float)
+        dp = (fp * max(n, 1))(*[a.ctypes.data_as(fp) for a in depth])
+        np_ = (fp * max(n, 1))(*[fp() if a is None else a.ctypes.data_as(fp) for a in normal])
+        self._chk(self._lib.pmhip_mesh_project(self._h, n, K, R, Cc, wh, dp, np_ if any(want) else None))
+        return list(zip(depth, normal))
+
+    def mesh_visibility(self, K, R, Cc, sizes, n_vertices, th_front_depth=0.985):
+        """The visibility test of `views.sample_mesh_with_visibility` for every (vertex, view) on the device (pmhip_mesh_visibility) -> (n_vertices, n_views) bool."""
+        K, R, Cc, wh = self._mesh_views(K, R, Cc, sizes)
+        n = len(wh)
+        words = (n + 31) // 32
+        bits = np.zeros((int(n_vertices), max(words, 1)), np.uint32)
+        self._chk(self._lib.pmhip_mesh_visibility(self._h, n, K, R, Cc, wh, bits, float(th_front_depth)))
+        return ((bits[:, np.arange(n) // 32] >> (np.arange(n) % 32).astype(np.uint32)) & 1).astype(bool) if n else np.zeros((int(n_vertices), 0), bool)
+
+    def mesh_release(self):
+        self._chk(self._lib.pmhip_mesh_release(self._h))
+
+    def mesh_tuning(self, box_pixels=0, batch_bytes=0):
+        """pmhip_mesh_set_tuning + pmhip_mesh_get_stats -> {batches, large_faces, device_us (of the last call), box_pixels, batch_bytes (in force)}; the results never
+        depend on it."""
+        self._chk(self._lib.pmhip_mesh_set_tuning(self._h, int(box_pixels), int(batch_bytes)))
+        out = np.zeros(5, np.uint64)
+        self._chk(self._lib.pmhip_mesh_get_stats(self._h, out))
+        return dict(zip(("batches", "large_faces", "box_pixels", "batch_bytes", "device_us"), (int(v) for v in out)))
 
     def scene_set_color(self, idx, bgr):
         """8-bit BGR image of a view at depth-map resolution (only fusion with bEstimateColor reads it)."""

@@ -506,3 +506,175 @@ def estimate_normal_map(K, depth):
         out = (v * a[..., None]).astype(f32)
     out[~good] = 0
     return out
+
+
+# ---- a mesh rendered into depth and normal maps (`--mesh-file`, `--export-depth-maps-name`) --------------------------------------------------------
+
+def compute_normal_vertices(vertices, faces):
+    """`Mesh::ComputeNormalVertices` (libs/MVS/Mesh.cpp:356-371, the active branch): per vertex the float sum of the unnormalised cross products (v1 - v0) x (v2 - v0) of
+    its faces IN FACE ORDER (and, within a face, corner order: a face that names a vertex twice adds twice), then cv::normalize = v * (1 / |v|) with the norm and the
+    product in double -- which leaves a zero sum (an isolated vertex, or only degenerate faces) zero."""
+    V = np.ascontiguousarray(vertices, f32).reshape(-1, 3)
+    F = np.asarray(faces, np.int64).reshape(-1, 3)
+    a, b = (V[F[:, 1]] - V[F[:, 0]]).astype(f32), (V[F[:, 2]] - V[F[:, 0]]).astype(f32)
+    t = np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1).astype(f32)   # cv::Point3_::cross
+    n = np.zeros_like(V)
+    np.add.at(n, F.ravel(), np.repeat(t, 3, axis=0))                 # ufunc.at applies the records one after the other: face-major, corner-minor
+    return _normalized_f32(n)
+
+
+def _normalized_f32(v):
+    """cv::normalize of float 3-vectors: the squares summed left to right in double, v * (nv ? 1 / nv : 0) in double, narrowed."""
+    d = np.asarray(v, f32).astype(np.float64)
+    nv = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        a = np.where(nv != 0, 1.0 / np.where(nv != 0, nv, 1.0), 0.0)
+        return (d * a[..., None]).astype(f32)
+
+
+def mesh_vertex_records(K, R, C, w, h, vertices):
+    """`TRasterMeshBase::ProjectVertex` for every vertex (libs/MVS/Mesh.h:303-306) -> (pti (n,2) f32, z (n,) f32, ok (n,) bool, front (n,) bool).
+    ptc = R (X - C) in double, a cv::Matx product (accumulated from 0, left to right); pti = (K02 + K00 ptc.x / ptc.z, K12 + K11 ptc.y / ptc.z) in double, narrowed to
+    float; `ok`: ptc.z > 0 (the double) and isInsideWithBorder<float,3>(pti); `front`: ptc.z > 0, where pti means something.  z = (float)ptc.z."""
+    K = np.asarray(K, np.float64); R = np.asarray(R, np.float64); C = np.asarray(C, np.float64)
+    X = np.ascontiguousarray(vertices, f32).reshape(-1, 3).astype(np.float64)
+    d = X - C
+    ptc = np.stack([((0.0 + R[i, 0] * d[:, 0]) + R[i, 1] * d[:, 1]) + R[i, 2] * d[:, 2] for i in range(3)], 1)
+    front = ptc[:, 2] > 0
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        zs = np.where(front, ptc[:, 2], 1.0)
+        pti = np.stack([K[0, 2] + K[0, 0] * (ptc[:, 0] / zs), K[1, 2] + K[1, 1] * (ptc[:, 1] / zs)], 1).astype(f32)
+        z = ptc[:, 2].astype(f32)
+    ok = front & (pti[:, 0] >= f32(3)) & (pti[:, 1] >= f32(3)) & (pti[:, 0] <= f32(w - 4)) & (pti[:, 1] <= f32(h - 4))
+    return pti, z, ok, front
+
+
+def _edge_f32(a0, a1, b0, b1, c0, c1):
+    """EdgeFunction(a, b, c) (libs/Common/Util.inl:602-604) on arrays: (c - a).cross(b - a), differences in float, the cross product in double, narrowed."""
+    return ((c0 - a0).astype(f32).astype(np.float64) * (b1 - a1).astype(f32).astype(np.float64)
+            - (c1 - a1).astype(f32).astype(np.float64) * (b0 - a0).astype(f32).astype(np.float64)).astype(f32)
+
+
+def mesh_candidates(pti, z, ok, faces, w, h):
+    """Every (face, pixel) pair `TImage::RasterizeTriangleBary` (CULL) hands to the raster functor for the faces of a mesh whose vertices are all `ok`, the arithmetic of
+    `_raster_face` on flat arrays -> (face (m,), pixel index y * w + x (m,), z (m,) f32, pb (m,3) f32 perspective-correct barycentrics), faces ascending."""
+    F = np.asarray(faces, np.int64).reshape(-1, 3)
+    fi = np.nonzero(ok[F].all(1))[0] if len(F) else np.zeros(0, np.int64)
+    P = pti[F[fi]]                                                           # (n, 3, 2)
+    Z = z[F[fi]]
+    x = P[..., 0]; y = P[..., 1]
+    mnx, mxx, mny, mxy = x.min(1), x.max(1), y.min(1), y.max(1)
+    keep = ~((mxx < 0) | (mnx > f32(w - 1)) | (mxy < 0) | (mny > f32(h - 1)))
+    x0 = np.maximum(np.floor(mnx).astype(np.int64), 0); x1 = np.minimum(np.ceil(mxx).astype(np.int64), w - 1)
+    y0 = np.maximum(np.floor(mny).astype(np.int64), 0); y1 = np.minimum(np.ceil(mxy).astype(np.int64), h - 1)
+    area = _edge_f32(x[:, 0], y[:, 0], x[:, 1], y[:, 1], x[:, 2], y[:, 2])
+    keep &= ~(area <= 0)
+    with np.errstate(divide="ignore"):
+        inv = (f32(1) / area).astype(f32)
+    bw = x1 - x0 + 1
+    cnt = np.where(keep, bw * (y1 - y0 + 1), 0)
+    k = np.repeat(np.arange(len(fi)), cnt)                                   # candidate -> kept face
+    off = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    px = x0[k] + off % np.maximum(bw[k], 1); py = y0[k] + off // np.maximum(bw[k], 1)
+    pxf, pyf = px.astype(f32), py.astype(f32)
+    X, Y, Zk, invk = x[k], y[k], Z[k], inv[k]
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        b1 = (_edge_f32(X[:, 1], Y[:, 1], X[:, 2], Y[:, 2], pxf, pyf) * invk).astype(f32)
+        b2 = (_edge_f32(X[:, 2], Y[:, 2], X[:, 0], Y[:, 0], pxf, pyf) * invk).astype(f32)
+        b3 = (_edge_f32(X[:, 0], Y[:, 0], X[:, 1], Y[:, 1], pxf, pyf) * invk).astype(f32)
+        inside = ~(b1 < 0) & ~(b2 < 0) & ~(b3 < 0)
+        z0, z1, z2 = Zk[:, 0], Zk[:, 1], Zk[:, 2]
+        p0 = ((b1 * z1).astype(f32) * z2).astype(f32); p1 = ((b2 * z0).astype(f32) * z2).astype(f32); p2 = ((b3 * z0).astype(f32) * z1).astype(f32)
+        invd = (f32(1) / ((p0 + p1).astype(f32) + p2).astype(f32)).astype(f32)
+        p0 = (invd * p0).astype(f32); p1 = (invd * p1).astype(f32); p2 = (invd * p2).astype(f32)
+        zz = (((p0 * z0).astype(f32) + (p1 * z1).astype(f32)).astype(f32) + (p2 * z2).astype(f32)).astype(f32)
+    s = np.nonzero(inside)[0]
+    return fi[k[s]], (py[s] * w + px[s]), zz[s], np.stack([p0[s], p1[s], p2[s]], 1)
+
+
+def project_mesh(K, R, C, w, h, vertices, faces, vertex_normals=None):
+    """`Mesh::Project(camera, depthMap[, normalMap])` (libs/MVS/Mesh.cpp:3874-3885, :3927-3968) -> (depth (h,w) f32, normal (h,w,3) f32 | None).
+
+    A face is rendered when all three vertices have z > 0 and lie inside the image with a border of 3 (nothing is clipped); a pixel ends with the smallest z over the faces
+    that cover its centre, the lowest face index among bit-equal z (`depth == 0 || depth > z`, faces in index order: z is positive, so its bit pattern orders as its value
+    and the winner is the smallest (z bits, face index)).  The normal is R_float * normalized(n0 pb0 + n1 pb1 + n2 pb2) of the winner, zero where no face is."""
+    w, h = int(w), int(h)
+    F = np.asarray(faces, np.int64).reshape(-1, 3)
+    pti, z, ok, _ = mesh_vertex_records(K, R, C, w, h, vertices)
+    face, pix, zz, pb = mesh_candidates(pti, z, ok, F, w, h)
+    key = (zz.view(np.uint32).astype(np.uint64) << np.uint64(32)) | face.astype(np.uint64)
+    best = np.full(w * h, np.iinfo(np.uint64).max, np.uint64)
+    np.minimum.at(best, pix, key)
+    depth = np.where(best != np.iinfo(np.uint64).max, (best >> np.uint64(32)).astype(np.uint32).view(f32), f32(0)).astype(f32).reshape(h, w)
+    if vertex_normals is None:
+        return depth, None
+    N = np.ascontiguousarray(vertex_normals, f32).reshape(-1, 3)
+    win = np.nonzero(key == best[pix])[0]
+    fw, pw = F[face[win]], pb[win]
+    with np.errstate(over="ignore", invalid="ignore"):
+        n = ((N[fw[:, 0]] * pw[:, 0:1]).astype(f32) + (N[fw[:, 1]] * pw[:, 1:2]).astype(f32)).astype(f32)
+        n = _normalized_f32((n + (N[fw[:, 2]] * pw[:, 2:3]).astype(f32)).astype(f32))
+        Rf = np.asarray(R, np.float64).astype(f32)
+        rot = np.stack([(((f32(0) + Rf[i, 0] * n[:, 0]).astype(f32) + Rf[i, 1] * n[:, 1]).astype(f32) + Rf[i, 2] * n[:, 2]).astype(f32) for i in range(3)], 1)
+    normal = np.zeros((h * w, 3), f32)
+    normal[pix[win]] = rot
+    return depth, normal.reshape(h, w, 3)
+
+
+def mesh_visibility(K, R, C, w, h, vertices, depth, th_front_depth=0.985):
+    """The vertex loop of `Scene::SampleMeshWithVisibility` (libs/MVS/Scene.cpp:656-667) for one image -> (n,) bool: xz = (Point3f)TransformPointW2I3(vertex); visible
+    when xz.z > 0, isInsideWithBorder<float,1>(x) and xz.z * thFrontDepth < depthMap(ROUND2INT(x)), ROUND2INT = floor(x + .5f) in float."""
+    pti, z, _, front = mesh_vertex_records(K, R, C, w, h, vertices)
+    inside = front & (z > 0) & (pti[:, 0] >= f32(1)) & (pti[:, 1] >= f32(1)) & (pti[:, 0] <= f32(w - 2)) & (pti[:, 1] <= f32(h - 2))
+    px = np.where(inside, np.floor((pti[:, 0] + f32(0.5)).astype(f32)), 0).astype(np.int64)
+    py = np.where(inside, np.floor((pti[:, 1] + f32(0.5)).astype(f32)), 0).astype(np.int64)
+    return inside & ((z * f32(th_front_depth)).astype(f32) < np.asarray(depth, f32)[py, px])
+
+
+def mesh_sample_views(scene, max_resolution=320, sizes=None):
+    """The cameras `SampleMeshWithVisibility` renders into (Scene.cpp:648-653): per valid image (K, R, C, w, h) at computeResize(size, nMaxResolution / larger side) with
+    nMaxResolution = computeMaxResolution(w, h, level 0, 0, maxResolution); `sizes`: the images' own (width, height) (default `scene.sizes`, else the cameras')."""
+    sizes = sizes if sizes is not None else getattr(scene, "sizes", None)
+    out = {}
+    for i, im in enumerate(scene.images):
+        if not im.is_valid():
+            continue
+        W, H = sizes[i] if sizes is not None else scene.camera(i)[3:]
+        res, _ = compute_max_resolution(W, H, 0, 0, max_resolution)
+        scale = res / W if W > H else res / H
+        out[i] = scene.camera(i, (int(np.rint(W * scale)), int(np.rint(H * scale))))    # computeResize (Types.inl:2440-2445): saturate_cast<int> = cvRound, ties to even
+    return out
+
+
+def swap_remove_order(keep):
+    """Indices that remain, in their final order, after the backward loop `RFOREACH(i) if (!keep[i]) RemoveAt(i)` of cList, whose RemoveAt moves the LAST element into
+    the hole (libs/Common/List.h; the order DESIGN 4.6 derives for the crop)."""
+    order = list(range(len(keep)))
+    for i in range(len(keep) - 1, -1, -1):
+        if not keep[i]:
+            order[i] = order[-1]
+            order.pop()
+    return np.array(order, np.int64)
+
+
+def sample_mesh_with_visibility(scene, vertices, faces, max_resolution=320, project=None, visibility=None):
+    """`Scene::SampleMeshWithVisibility` (libs/MVS/Scene.cpp:634-677): the sparse cloud a mesh stands in for -> (points (n,3) f32, view_start (n+1,) int64, views (m,)
+    uint32), in the reference's final order.  Every vertex carries the images in which it lies in front of the depth map rendered from the mesh (at most `max_resolution`
+    pixels wide), sorted; vertices seen by fewer than 2 images are removed by the reference's backward swap-remove loop (`swap_remove_order`).
+    `project(K, R, C, w, h) -> depth` replaces the host render (`project_mesh`), `visibility(cams) -> (n_vertices, n_cams) bool` the whole test (the engine's bitset);
+    `cams` is the list of (K, R, C, w, h) of the valid images in index order."""
+    V = np.ascontiguousarray(vertices, f32).reshape(-1, 3)
+    cams = mesh_sample_views(scene, max_resolution)
+    ids = sorted(cams)
+    if visibility is not None:
+        vis = np.asarray(visibility([cams[i] for i in ids]), bool)
+    else:
+        vis = np.zeros((len(V), len(ids)), bool)
+        for k, i in enumerate(ids):
+            K, R, C, w, h = cams[i]
+            depth = project(K, R, C, w, h) if project is not None else project_mesh(K, R, C, w, h, V, faces)[0]
+            vis[:, k] = mesh_visibility(K, R, C, w, h, V, depth)
+    order = swap_remove_order(vis.sum(1) >= 2)
+    vis = vis[order]
+    start = np.concatenate([[0], np.cumsum(vis.sum(1))]).astype(np.int64)
+    return V[order].copy(), start, np.asarray(ids, np.uint32)[np.nonzero(vis)[1]]
