@@ -364,9 +364,11 @@ int pmhip_resize(pmhip_engine* e, int kind, const float* src, int w, int h, int 
  *   MASK_LEVEL    one 8-bit image, INTER_NEAREST
  *   SKEW          nImg images -> the folded anti-diagonal-major copy, same size
  *   QUAD          nImg images -> nImg quad images of (w + h - 1) * h float4 entries, same size
+ *   DEPTH_QUADS   one depth map (w, h >= 2) -> the quad copy the geometric rounds derive of a source depth map: w * h float4 entries, entry (lx, ly) =
+ *                 {D(lx,ly), D(lx+1,ly), D(lx,ly+1), D(lx+1,ly+1)} as bit patterns at ((lx + ly) mod w) * h + ly, 0 for texels the map does not have
  * nImg = 1 except where it is named.  PMHIP_E_SIZE for sizes the kind does not take. */
 enum { PMHIP_RESAMPLE_AREA = 0, PMHIP_RESAMPLE_UPSAMPLE = 1, PMHIP_RESAMPLE_NEAREST_DOWN = 2, PMHIP_RESAMPLE_NEAREST_UP = 3, PMHIP_RESAMPLE_MASK_LEVEL = 4,
-       PMHIP_RESAMPLE_SKEW = 5, PMHIP_RESAMPLE_QUAD = 6 };
+       PMHIP_RESAMPLE_SKEW = 5, PMHIP_RESAMPLE_QUAD = 6, PMHIP_RESAMPLE_DEPTH_QUADS = 7 };
 int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, void* dst, int dw, int dh, int arg, int nImg);
 
 #ifdef __cplusplus

@@ -222,6 +222,23 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 		const unsigned long long needBal = __ballot(need);
 		if (needBal == 0ull) break;
 		PM_TICK(1); PM_COUNT(8, __popcll(needBal)); PM_HIST(__popcll(needBal) / G);
+		// -- geometric pass: the depth-map footprints of ALL of the lane's views are requested now that the hypothesis is known -- their addresses need its depth and the view,
+		//    not the taps -- and travel under the smoothness factors, the first view's homography, the corner test and two row issues; they are older than every tap row, so
+		//    the first row's wait covers them and the term finds them in registers (it was a dependent L2 round trip at the end of every evaluation: DESIGN.md 4.1).  A view
+		//    that ends early (corner test, a tap outside, no texture) drops its footprint unused.
+		typename std::conditional<GEO, PMGeoReq, PMNoGeoReq>::type greq[GEO ? VPL : 1];   // (nothing in the photometric kernel)
+		if constexpr (GEO) {
+			const PM_LDS PMPix* P = pm_launder(s_pixg);
+			const double gX0x = P->X0x, gX0y = P->X0y;
+#pragma unroll
+			for (int u = 0; u < VPL; ++u) {
+				const int vw = v + u * G;
+				PM_CENSUS_GEO(vw);
+				pm_geo_request(need && vw < t.nSrc, hotBase + vw * NBD + PM_SRC_HOT, gX0x, gX0y, hd, greq[u]);
+			}
+			PM_CENSUS_GEO(-1);
+			PM_GEO_HOLD();
+		}
 		// -- smoothness factors of the hypothesis plane w.r.t. the close neighbours, DepthMap.cpp:524-533, one neighbour per lane row 0..3; they reach the pixel's other
 		//    lanes through its state in LDS: one 4-byte write here, one 16-byte read per view where the score takes them (pm_score_view) -- fewer instructions than four
 		//    ds_bpermute_b32 with their lane addresses, and no registers held across the tap rows
@@ -255,7 +272,10 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 				const int vw = v + u * G;
 				if (need && vw < t.nSrc) {
 					PM_CENSUS_VIEW(t.w, G, u);
-					const float s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, 1.f, 1.f, 1.f, 1.f, 0.f,
+					float s1;
+					if constexpr (GEO) s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, 1.f, 1.f, 1.f, 1.f, 0.f,
+						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P), greq, u, VPL);
+					else s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, 1.f, 1.f, 1.f, 1.f, 0.f,
 						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P));
 					PM_CENSUS_VIEW_END();
 					if (s1 < sc) { sc2 = sc; sc = s1; } else if (s1 < sc2) sc2 = s1;
@@ -313,7 +333,16 @@ __global__ __launch_bounds__(64, (GEO ? PM_BAND_MINWAVES : PM_BAND_MINWAVES_PHOT
 	const PMTask& t = tasks[vby];
 	const PMImgBuf rs = pm_make_imgbuf(t);
 	const int lane = threadIdx.x;
-	for (int i = lane; i < NV * NBD; i += 64) s_src[i] = ((const double*)&t.src[i / NBD])[i % NBD];
+	for (int i = lane; i < NV * NBD; i += 64) {
+		double e = ((const double*)&t.src[i / NBD])[i % NBD];
+		// the sweep reads the source depth maps through their quad copies: the copy's pointer takes the map's slot of the block
+		if constexpr (GEO) if (i % NBD == PM_SRC_HOT + 12) {
+			const PMSrcView& sv = t.src[i / NBD];
+			const float4* q = sv.depth != nullptr ? pm_task_geoq(t) + sv.dqBase : nullptr;   // (the host refuses a geometric launch of this kernel without the copies)
+			e = *(const double*)&q;
+		}
+		s_src[i] = e;
+	}
 	const int g = lane % PPW, v = lane / PPW;   // view-major: a quad of lanes = four neighbouring pixels, one source view
 	const int w = t.w, h = t.h;
 	const PMStepPix sp = pm_step_pixel<TILED>(st, w, h, (int)vbx * PPW + g);

@@ -170,6 +170,9 @@ struct SceneMem {
 	DevBuf<float> d_imgS[4];   // folded anti-diagonal-major copies (PMTask::refS: the reference patch of a sweep visit), w_l*h_l floats per image
 	DevBuf<float4> d_imgQ[4];  // anti-diagonal-major quad images (PMSrcView::imgQ): texel (u,v)'s entry at (u+v)*h_l + v, (w_l+h_l-1)*h_l entries of 16 bytes per image
 	DevBuf<float> d_depth, d_normal, d_conf, d_snap;
+	// geometric rounds: the quad copies (PMSrcView::dqBase) of the depth maps the running call reads as sources, one after the other, 16 bytes per pixel (grow only).
+	// The row-major maps stay the truth -- callers write them through pmhip_scene_device_ptr too -- so the copies are derived at the head of every geometric call.
+	DevBuf<float4> d_geoQ;
 	// ignore masks (nIgnoreMaskLabel): per level [nImages][P_l] bytes, allocated with the first mask; maskMode -1 = on iff a mask is set
 	DevBuf<unsigned char> d_mask[4]; std::vector<unsigned char> hasMask; bool maskDirty = false; int maskMode = -1;
 	// FilterDepthMap staging: filtered depth/conf of every view (committed after all views are filtered) and splat buffers
@@ -650,6 +653,7 @@ uint64_t pmhip_scene_bytes(pmhip_engine* e) {
 		if (e->d_mask[l]) b += (size_t)e->lw(l) * e->lh(l) * N;
 	}
 	if (e->d_depth) b += sizeof(float) * P0 * N * 6;                       // depth, normal (3), confidence, previous round's depth
+	b += sizeof(float4) * e->d_geoQ.n;                                     // quad copies of the source depth maps of the geometric rounds
 	if (e->d_fdepth) b += sizeof(float) * P0 * N * 2 + P0 * N;             // FilterDepthMap staging
 	if (e->d_splat) b += sizeof(unsigned long long) * e->splatPix * PMF_MAXN * (size_t)e->splatCap;
 	if (e->batchCap) {
@@ -822,11 +826,12 @@ int pmhip_resize(pmhip_engine* e, int kind, const float* src, int w, int h, int 
 // read back whole, so whatever the caller put into the entries a kernel does not write (a quad image's unused corners) comes back untouched -- or not.
 int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, void* dst, int dw, int dh, int arg, int nImg) {
 	if (!e || !src || !dst) return PMHIP_E_ARG;
-	if (kind < PMHIP_RESAMPLE_AREA || kind > PMHIP_RESAMPLE_QUAD) { e->err = "pmhip_resample: unknown kind"; return PMHIP_E_ARG; }
+	if (kind < PMHIP_RESAMPLE_AREA || kind > PMHIP_RESAMPLE_DEPTH_QUADS) { e->err = "pmhip_resample: unknown kind"; return PMHIP_E_ARG; }
 	if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || nImg < 1) { e->err = "pmhip_resample: empty image"; return PMHIP_E_SIZE; }
-	const bool factor = kind == PMHIP_RESAMPLE_AREA || kind == PMHIP_RESAMPLE_NEAREST_DOWN, same = kind == PMHIP_RESAMPLE_SKEW || kind == PMHIP_RESAMPLE_QUAD;
+	const bool factor = kind == PMHIP_RESAMPLE_AREA || kind == PMHIP_RESAMPLE_NEAREST_DOWN, same = kind == PMHIP_RESAMPLE_SKEW || kind == PMHIP_RESAMPLE_QUAD || kind == PMHIP_RESAMPLE_DEPTH_QUADS;
 	if (factor && (arg < 1 || dw != (int)nearbyint((double)sw / arg) || dh != (int)nearbyint((double)sh / arg))) { e->err = "pmhip_resample: the destination is not cvRound(size / factor)"; return PMHIP_E_SIZE; }
 	if (same && (dw != sw || dh != sh)) { e->err = "pmhip_resample: skew and quad keep the size"; return PMHIP_E_SIZE; }
+	if (kind == PMHIP_RESAMPLE_DEPTH_QUADS && (nImg != 1 || sw < 2 || sh < 2)) { e->err = "pmhip_resample: one depth map of at least 2 x 2"; return PMHIP_E_SIZE; }
 	if (nImg != 1 && !(kind == PMHIP_RESAMPLE_AREA || same)) { e->err = "pmhip_resample: one image for this kind"; return PMHIP_E_ARG; }
 	HIPCHK(e, hipSetDevice(e->device));
 	const size_t ps = (size_t)sw * sh, pd = (size_t)dw * dh;
@@ -837,6 +842,7 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 	case PMHIP_RESAMPLE_NEAREST_DOWN: bs = ps * 16; bd = pd * 16; break;
 	case PMHIP_RESAMPLE_MASK_LEVEL: bs = ps; bd = pd; break;
 	case PMHIP_RESAMPLE_QUAD: bd = (size_t)(dw + dh - 1) * dh * 16 * nImg; break;
+	case PMHIP_RESAMPLE_DEPTH_QUADS: bd = pd * 16; break;
 	default: break;
 	}
 	DevBuf<unsigned char> ds, dd; DevBuf<PMUpTask> du;
@@ -856,6 +862,7 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 	case PMHIP_RESAMPLE_NEAREST_UP: launchNearestUpF(e->stream, fs, fd, sw, sh, dw, dh); break;
 	case PMHIP_RESAMPLE_MASK_LEVEL: launchMaskLevel(e->stream, ds, dd, sw, sh, dw, dh); break;
 	case PMHIP_RESAMPLE_SKEW: launchSkew(e->stream, fs, fd, sw, sh, nImg); break;
+	case PMHIP_RESAMPLE_DEPTH_QUADS: launchDepthQuads(e->stream, fs, (float4*)fd, sw, sh); break;
 	default: launchQuad(e->stream, fs, (float4*)fd, sw, sh, nImg); break;
 	}
 	HIPCHK(e, hipGetLastError());

@@ -42,6 +42,10 @@ static void launchSkew(hipStream_t st, const float* src, float* dst, int w, int 
 static void launchQuad(hipStream_t st, const float* src, float4* dst, int w, int h, int nImg) {
 	hipLaunchKernelGGL(pm_quad_kernel, dim3(resampleBlocks((size_t)w * h * nImg, 65535)), dim3(256), 0, st, src, dst, w, h, nImg);
 }
+// the quad copy of one source depth map of the geometric rounds (PMSrcView::dqBase)
+static void launchDepthQuads(hipStream_t st, const float* map, float4* dst, int dw, int dh) {
+	hipLaunchKernelGGL(pm_depth_quads_kernel, dim3(resampleBlocks((size_t)dw * dh, 8192)), dim3(256), 0, st, (const uint32_t*)map, (PMQuadBits*)dst, dw, dh);
+}
 static void launchMaskLevel(hipStream_t st, const unsigned char* src, unsigned char* dst, int sw, int sh, int dw, int dh) {
 	hipLaunchKernelGGL(pm_mask_level_kernel, dim3(resampleBlocks((size_t)dw * dh, 4096)), dim3(256), 0, st, src, dst, sw, sh, dw, dh);
 }
@@ -262,6 +266,41 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 	const size_t P0s = (size_t)e->w * e->h;
 	// the staging buffers are reused by the next call (and by the next size class): make sure the previous copies are done
 	HIPCHK(e, hipStreamSynchronize(e->stream));
+	// geometric round: the depth map a source view is read through -- the one the caller installed (pmhip_scene_set_source_depth), its own previous-round map (a view of
+	// its own size) or its part of the scene's snapshot -- and the quad copies of exactly the maps this call reads, derived now, on the engine's stream, before the
+	// view groups fork: the row-major maps are written by commits, copies, uploads and by callers through their device pointers, so no copy outlives a call
+	struct GeoMap { const float* map; int dw, dh; size_t ofs; };
+	std::vector<GeoMap> geoMaps;
+	auto geoMapOf = [&](int nbId) -> GeoMap {
+		const SceneView& sv = e->views[nbId];
+		if (sv.sDepth) return {sv.sDepth, sv.dw, sv.dh, 0};
+		if (sv.sw) return {sv.oSnap, sv.sw, sv.sh, 0};
+		return {e->d_snap + P0s * nbId, e->w, e->h, 0};
+	};
+	auto geoQuadsOf = [&](const float* map) -> size_t {   // first entry of the map's copy in d_geoQ
+		for (const GeoMap& m : geoMaps) if (m.map == map) return m.ofs;
+		return 0;
+	};
+	// (a batch whose every launch goes to the speculative kernels -- wideBatch without tiles, pass B below -- never runs pm_sweep2_kernel, the only reader of the copies:
+	// it derives none and holds no memory for them; pass B refuses a geometric launch of that kernel without them, should the two rules ever part)
+	const bool quadsDerived = geo && !(wideBatch && !(e->tileW > 0 && e->tileH > 0));
+	if (quadsDerived) {
+		std::vector<char> seen((size_t)e->nImages, 0);
+		size_t total = 0;
+		for (int b = 0; b < nB; ++b) {
+			const SceneView& v = e->views[ids[b]];
+			for (int k = 0; k < v.nNb; ++k) if (!seen[v.nb[k]]) {
+				seen[v.nb[k]] = 1;
+				GeoMap m = geoMapOf(v.nb[k]);
+				m.ofs = total; total += (size_t)m.dw * m.dh;
+				geoMaps.push_back(m);
+			}
+		}
+		if (total > 0xFFFFFFFFull) { e->err = "geometric round: the quad copies of the source depth maps of one call hold 2^32 entries or more (PMSrcView::dqBase)"; return PMHIP_E_SIZE; }
+		HIPCHK(e, e->d_geoQ.reserve(total));
+		for (const GeoMap& m : geoMaps) launchDepthQuads(e->stream, m.map, e->d_geoQ + m.ofs, m.dw, m.dh);
+		HIPCHK(e, hipGetLastError());
+	}
 	for (int l = S; l >= 0; --l) {
 		const int lw = lvlSize(cw, l), lh = lvlSize(ch, l);
 		const size_t Pl = (size_t)lw * lh;
@@ -274,6 +313,7 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 			const SceneView& v = e->views[id];
 			PMTask& t = ht[b];
 			memset(&t, 0, sizeof(t));
+			if (quadsDerived) { const uintptr_t q = (uintptr_t)(const float4*)e->d_geoQ; t.geoQLo = (uint32_t)q; t.geoQHi = (uint32_t)((unsigned long long)q >> 32); }
 			if (l == 0) {
 				t.depth = e->depthOf(id); t.normal = e->normalOf(id); t.conf = e->confOf(id);
 				t.prior = (S > 0) ? e->d_lvl[0] + P0 * b : nullptr;
@@ -325,9 +365,9 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 					// snapshot, or the camera stored with the map the caller installed (pmhip_scene_set_source_depth), whose size may differ too
 					double tm[9], vv[3], RdT[9], iKd[9], t2[9], KdRd[9];
 					const double* Kd = Kj; const double* Rd = sv.R; const double* Cd = sv.C;
-					if (sv.sDepth) { s.depth = sv.sDepth; s.dw = sv.dw; s.dh = sv.dh; Kd = sv.Kd; Rd = sv.Rd; Cd = sv.Cd; }
-					else if (sv.sw) { s.depth = sv.oSnap; s.dw = sv.sw; s.dh = sv.sh; }   // its own previous-round map (own size, own camera = Kj at level 0)
-					else { s.depth = e->d_snap + P0s * v.nb[k]; s.dw = e->w; s.dh = e->h; }
+					if (sv.sDepth) { Kd = sv.Kd; Rd = sv.Rd; Cd = sv.Cd; }   // (a view's own previous-round map has its own camera = Kj at level 0)
+					const GeoMap gm = geoMapOf(v.nb[k]);
+					s.depth = gm.map; s.dqBase = (unsigned)geoQuadsOf(gm.map); s.dw = gm.dw; s.dh = gm.dh;
 					mul33(Kd, Rd, KdRd);
 					mul33(KdRd, R0T, tm); for (int i = 0; i < 9; ++i) s.Tl[i] = (float)tm[i];
 					for (int i = 0; i < 3; ++i) dC[i] = v.C[i] - Cd[i];
@@ -402,6 +442,7 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 	if (nGeometricIter < 0 && p.nEstimationGeometricIters) thFinal *= 1.333f;
 	size_t evSweep[16] = {}; bool evOpen[16] = {};
 	size_t nLaunched = 0;
+	const char* sweepErr = nullptr;
 	const auto hostT0 = std::chrono::steady_clock::now();
 	auto issue = [&](int g, const Step& sp) -> bool {
 		const int l = sp.l, s0 = g0(g), nT = g0(g + 1) - s0;
@@ -448,6 +489,7 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 			const bool wide = (wideBatch && !(tiled && npx > e->widePixels)) || (maxSrc <= 8 && npx <= wpx);
 			int hyps = (wideBatch && e->wideHyps > 0) ? e->wideHyps : ((nB <= 2 || npx <= e->wide8Pixels) ? 8 : 2);
 			if (tiled && hyps == 8) hyps = 2;   // (the eight-wide kernel walks whole anti-diagonals of the map)
+			if (geo && !wide && !quadsDerived) { sweepErr = "geometric round: a pm_sweep2_kernel launch without the quad copies of the source depth maps"; return false; }
 			++nLaunched;
 #ifdef PM_PROBES
 			for (int r = 1; r < g_probeRepeat; ++r)   // (measurement builds only) the same diagonal again, back to back: what does a launch find in the caches its predecessor filled?
@@ -470,7 +512,7 @@ static int estimateClass(pmhip_engine* e, const int32_t* ids, int nB, int cw, in
 	// the host feeds the groups' streams in turn, step by step
 	for (long i = 0; i < nSteps; ++i)
 		for (int g = 0; g < NG; ++g)
-			if (!issue(g, steps[i])) { e->err = "sweep kernel: (lanes per pixel, views per lane) mapping not instantiated"; return PMHIP_E_ARG; }
+			if (!issue(g, steps[i])) { e->err = sweepErr ? sweepErr : "sweep kernel: (lanes per pixel, views per lane) mapping not instantiated"; return PMHIP_E_ARG; }
 	if (NG > 1) for (int g = 0; g < NG; ++g) { HIPCHK(e, hipEventRecord(e->joinEv[g], gs(g))); HIPCHK(e, hipStreamWaitEvent(e->stream, e->joinEv[g], 0)); }
 	evEndOn(e, evWall, e->stream);
 	HIPCHK(e, hipGetLastError());

@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <type_traits>
 #include "pm_math.h"
 
 #define PM_MAX_SRC 16
@@ -55,13 +56,16 @@ struct PMSrcView {
 	double Hl[9];         // K_j R_j R_0^T          (ViewData::Init, DepthMap.h:175-185)
 	double Hm[3];         // K_j R_j (C_0 - C_j)
 	int w, h;             // size of the source image at this level
-	unsigned qBase, qPad; // first entry of this view's quad image in the level's quad buffer (PMTask::qArr); unused for a view with its own image size
+	unsigned qBase;       // first entry of this view's quad image in the level's quad buffer (PMTask::qArr); unused for a view with its own image size
+	unsigned dqBase;      // geometric pass: first entry of the quad copy of `depth` (below) in the call's buffer of quad copies (pm_task_geoq), if the call derived them
 	// geometric block, 14 doubles: transforms of the consistency term and the source view's depth-map (nullable; geometric pass) with its own
 	// size: the map is addressed through cameraDepthMap (Tl..Tn), not through the image's camera (DepthMap.h:170-171, DepthMap.cpp:535-551)
 	float Tl[9], Tm[3], Tr[9], Tn[3];
-	const float* depth;
-	int dw, dh;
-	const float* img;     // source image at this pyramid level, row-major
+	const float* depth;   // the map, row-major (the snapshot itself).  pm_sweep2_kernel puts the map's quad copy (pm_task_geoq + dqBase: folded anti-diagonal-major,
+	                      // pm_dq_index; derived from this map at the head of every geometric call that runs that kernel) into this slot of its LDS copy of the block; the init
+	                      // kernel walks rows and the speculative kernels are chain-bound: both read the row-major map
+	int dw, dh;           // the map's size
+	const float* img;    // source image at this pyramid level, row-major
 	const float4* imgQ;   // anti-diagonal-major "quad" image: entry (u,v) = {I(u,v), I(u+1,v), I(u,v+1), I(u+1,v+1)} -- the four texels of a bilinear
 	                      // sample in ONE 16-byte load (the window-less tap rows are bound by the number of vector-memory instructions, not by bytes:
 	                      // the stride-2 taps of a patch never share texels, so the quad image is read at the same byte rate as the plain one)
@@ -69,7 +73,7 @@ struct PMSrcView {
 #define PM_SRC_HOT 14     // doubles
 #define PM_SRC_GEO 14
 static_assert(offsetof(PMSrcView, Hm) == 72 && offsetof(PMSrcView, w) == 96 && offsetof(PMSrcView, qBase) == 104 && offsetof(PMSrcView, Tl) == 8 * PM_SRC_HOT
-	&& offsetof(PMSrcView, depth) == 8 * PM_SRC_HOT + 96 && offsetof(PMSrcView, dw) == 8 * PM_SRC_HOT + 104 && offsetof(PMSrcView, img) == 8 * (PM_SRC_HOT + PM_SRC_GEO), "PMSrcView layout");
+	&& offsetof(PMSrcView, depth) == 8 * PM_SRC_HOT + 96 && offsetof(PMSrcView, dw) == 8 * PM_SRC_HOT + 104 && offsetof(PMSrcView, img) == 8 * (PM_SRC_HOT + PM_SRC_GEO) && sizeof(PMSrcView) == 8 * (PM_SRC_HOT + PM_SRC_GEO) + 16, "PMSrcView layout");
 struct PMTask {           // one reference view at one pyramid level
 	float* depth; float* normal; float* conf;
 	const float* prior;   // nullable: low-resolution depth prior at this level
@@ -79,10 +83,12 @@ struct PMTask {           // one reference view at one pyramid level
 	const unsigned char* mask; // nullable: ignore mask at this level, 0 = pixel is not estimated (DepthData::ApplyIgnoreMask + masked MapMatrix2ZigzagIdx)
 	// tiled sweeps only (pmhip_set_sweep_tiles; null otherwise): depth / normal / conf as the running sweep found them -- what a pixel reads of a neighbour in ANOTHER tile
 	const float* depthOld; const float* normalOld; const float* confOld;
-	int w, h, nSrc, pad0;
+	int w, h, nSrc;
+	uint32_t geoQLo;      // low half of the address of the call's quad copies of the source depth maps (pm_task_geoq; the high half is geoQHi): the two spare words of the struct,
+	                      // so that PMTask and PMSrcView keep the size and the alignment every kernel was tuned with
 	double Hr[9];         // K_0^-1
 	int hrUpper;          // 1 if Hr[1] == Hr[3] == Hr[6] == Hr[7] == 0 exactly (zero-skew K): products with those vanish exactly
-	int pad1;
+	uint32_t geoQHi;
 	double fx, fy, cx, cy;
 	float dMin, dMax, dMinSqr, dMaxSqr;
 	uint32_t k0, k1base;  // Philox key: (seed, viewID*0x9E3779B1 + pass)
@@ -90,6 +96,9 @@ struct PMTask {           // one reference view at one pyramid level
 	unsigned qCount, qPad; // its entries
 	PMSrcView src[PM_MAX_SRC];
 };
+static_assert(offsetof(PMTask, src) == 248 && sizeof(PMTask) == 248 + PM_MAX_SRC * sizeof(PMSrcView), "PMTask layout");
+// the call's buffer of quad copies (null if the call derived none: its launches all go to kernels that read the row-major maps)
+__host__ __device__ __forceinline__ const float4* pm_task_geoq(const PMTask& t) { return (const float4*)(uintptr_t)(((unsigned long long)t.geoQHi << 32) | t.geoQLo); }
 struct PMKParams {        // DepthEstimator ctor constants, DepthMap.cpp:397-406
 	float smoothBonusDepth, smoothBonusNormal, smoothSigmaDepth, smoothSigmaNormal;
 	float thMagnitudeSq, angle1Range, angle2Range, thConfSmall, thConfBig, thConfRand, thRobust;
@@ -400,7 +409,9 @@ inline unsigned blocksOfQuads(const std::array<unsigned, 64>& blk, unsigned long
 	}
 	return total;
 }
+inline void geoFlush();
 inline void flush() {
+	geoFlush();
 	if (recs.empty()) return;
 	std::stable_sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) { return a.key < b.key; });
 	Stat& s = stats[wgWidth];
@@ -420,8 +431,9 @@ inline void flush() {
 	}
 	recs.clear();
 }
+inline void geoReport();
 inline void report() {
-	flush();
+	flush(); geoReport();
 	for (auto& kv : stats) {
 		const Stat& s = kv.second; const double L = (double)s.loads, Q = 16.0 * L;
 		fprintf(stderr, "gather census: level width %d: %llu tap wave-loads, %.1f active lanes per load; blocks per load: view-major (shipped) %.2f, pixel-major %.2f, ratio %.3f; "
@@ -437,7 +449,43 @@ inline void trip() { enter(); trips[threadIdx.x & 63]++; }
 inline void view(int width, int G, int u) { wgWidth = width; wgG = G; curKey = (trips[threadIdx.x & 63] * 8u + (unsigned)u) * 8u; curRow = 0; armed = true; }
 inline void viewEnd() { armed = false; }
 inline void note(unsigned i0, unsigned i1, unsigned i2, unsigned i3, unsigned i4) { if (armed) recs.push_back(Rec{curKey + curRow++, threadIdx.x & 63u, {i0, i1, i2, i3, i4}}); }
+// The geometric term's gather (pm_geo_request): per lane row of a wave-load of pm_sweep2_kernel -- one (trip, source view): PPW pixels -- the 64-byte blocks its active lanes touch under the parent's
+// layout (row-major floats, two 8-byte loads on two rows) and under the three candidate orders of the quad copy; tools/gather_census.py --geo, profiles/geo_gather_census.txt.
+struct GeoRec { unsigned key, lane; int vw, lx, ly, dw, dh; };
+struct GeoStat { unsigned long long loads = 0, lanes = 0, rowMajor2 = 0, quadRow = 0, quadDiag = 0, quadFold = 0; };
+inline std::vector<GeoRec> geoRecs;
+inline GeoStat geoStat;
+inline int geoVw = -1; inline unsigned geoKey = 0;
+inline unsigned distinct(std::vector<unsigned long long>& b) { std::sort(b.begin(), b.end()); return (unsigned)(std::unique(b.begin(), b.end()) - b.begin()); }
+inline void geoFlush() {
+	std::stable_sort(geoRecs.begin(), geoRecs.end(), [](const GeoRec& a, const GeoRec& b) { return a.key < b.key; });
+	for (size_t i = 0; i < geoRecs.size();) {
+		size_t j = i; while (j < geoRecs.size() && geoRecs[j].key == geoRecs[i].key) ++j;
+		std::vector<unsigned long long> r0, r1, qr, qd, qf;
+		for (size_t r = i; r < j; ++r) {
+			const GeoRec& g = geoRecs[r];
+			const unsigned long long view = (unsigned long long)g.vw << 40, a = ((unsigned long long)g.ly * g.dw + g.lx) * 4ull, b = a + 4ull * g.dw;
+			r0.push_back(view | (a >> 6)); r0.push_back(view | ((a + 4) >> 6)); r1.push_back(view | (b >> 6)); r1.push_back(view | ((b + 4) >> 6));
+			qr.push_back(view | (((unsigned long long)g.ly * g.dw + g.lx) >> 2));
+			qd.push_back(view | (((unsigned long long)(g.lx + g.ly) * g.dh + g.ly) >> 2));
+			qf.push_back(view | (((unsigned long long)((g.lx + g.ly) % g.dw) * g.dh + g.ly) >> 2));
+		}
+		geoStat.loads++; geoStat.lanes += j - i;
+		geoStat.rowMajor2 += distinct(r0) + distinct(r1); geoStat.quadRow += distinct(qr); geoStat.quadDiag += distinct(qd); geoStat.quadFold += distinct(qf);
+		i = j;
+	}
+	geoRecs.clear();
 }
+inline void geoReport() {
+	geoFlush();
+	const double L = (double)geoStat.loads;
+	if (geoStat.loads) fprintf(stderr, "gather census: geometric term: %llu gathers of a lane row (16 pixels against one source view; a wave-load is four of them), %.1f lanes taking a sample per gather; 64-byte blocks per gather: row-major floats, two 8-byte loads (parent) %.2f; "
+		"quad copy row-major %.2f, anti-diagonal-major unfolded %.2f, folded %.2f\n", geoStat.loads, geoStat.lanes / L, geoStat.rowMajor2 / L, geoStat.quadRow / L, geoStat.quadDiag / L, geoStat.quadFold / L);
+}
+inline void geoView(int vw) { geoVw = vw; geoKey = trips[threadIdx.x & 63] * 8u + (unsigned)(vw >= 0 ? vw : 0); }
+inline void geoNote(int lx, int ly, int dw, int dh) { if (geoVw >= 0) geoRecs.push_back(GeoRec{geoKey, threadIdx.x & 63u, geoVw, lx, ly, dw, dh}); }
+}
+#define PM_CENSUS_GEO(vw) pm_census::geoView(vw)
 #define PM_CENSUS_TRIP() pm_census::trip()
 #define PM_CENSUS_VIEW(width, G, u) pm_census::view((width), (G), (u))
 #define PM_CENSUS_VIEW_END() pm_census::viewEnd()
@@ -455,6 +503,7 @@ __device__ __forceinline__ unsigned pm_mad24(int a, int b, unsigned c) { return 
 
 #ifndef PM_CENSUS_TRIP
 #define PM_CENSUS_TRIP()
+#define PM_CENSUS_GEO(vw)
 #define PM_CENSUS_VIEW(width, G, u)
 #define PM_CENSUS_VIEW_END()
 #endif
@@ -609,6 +658,97 @@ extern "C" __attribute__((visibility("default"))) void pm_debug_tap_census(unsig
 	for (int i = 0; i < 8; ++i) { if (out) out[i] = pm_tap_census[i / 4][i % 4]; if (reset) pm_tap_census[i / 4][i % 4] = 0; }
 }
 #endif
+// ---- the geometric term's gather (DepthMap.cpp:535-551) --------------------------------------------------------------------------------------------------------
+// The term samples the source view's previous-round depth map bilinearly at the projection of the hypothesis point.  The kernels read a QUAD COPY of that map
+// (pm_task_geoq + PMSrcView::dqBase, which pm_sweep2_kernel puts into the pointer slot of its LDS copy of the geometric block; derived from the row-major snapshot at the head of every
+// geometric call: pm_host_estimate.hip): entry (lx, ly) = {D(lx,ly), D(lx+1,ly), D(lx,ly+1),
+// D(lx+1,ly+1)} -- the bilinear footprint in ONE 16-byte load (it was two 8-byte loads on two rows) -- stored anti-diagonal-major and folded like PMTask::refS: entry
+// (lx, ly) at ((lx + ly) mod dw) * dh + ly, dw * dh entries.  The lanes of a wave are pixels of one anti-diagonal of the reference view; their projections into a source view
+// whose camera is turned like the reference's fall along an anti-diagonal there too, so neighbouring lanes read neighbouring entries (profiles/geo_gather_census.txt).
+// A sample is taken inside with border 1 (pm_inside1: lx <= dw - 2, ly <= dh - 2), so the entries of the last column and row are never read; the texels the map does
+// not have are 0.f there (pm_depth_quads_kernel).
+__device__ __forceinline__ unsigned pm_dq_index(int lx, int ly, int dw, int dh) {
+	int d = lx + ly;
+	if (d >= dw) { d -= dw; if (d >= dw) d %= dw; }
+	return (unsigned)d * (unsigned)dh + (unsigned)ly;
+}
+// What the address needs is the hypothesis depth and the view, not the taps: the request (transforms, projection, the two quotients, the inside test, the load) can be made
+// before the view's tap rows, and the term's arithmetic takes the texels where it always did.  The operations and their order are the reference's in both parts.
+struct PMGeoReq {
+	pm_f4v q;               // the entry: x0y0, x1y0, x0y1, x1y1
+	float x1x, x1y, Y2;     // position in the source depth map and the point's depth there
+	bool has, ok;           // the view has a depth map; the position takes a sample (Y2 > 0 and inside with border 1)
+};
+struct PMNoGeoReq {};
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PM_GEO_HOLD() asm volatile("" ::: "memory")   // the compiler sinks a load into the block of its only use unless something that may write memory follows it in its own block
+#else
+#define PM_GEO_HOLD() do {} while (0)
+#endif
+__device__ __forceinline__ void pm_geo_request(bool on, const double* geoTab, double X0x, double X0y, float depth, PMGeoReq& r) {
+	r.has = false; r.ok = false; r.x1x = 0.f; r.x1y = 0.f; r.Y2 = 0.f;
+	r.q.x = 0.f; r.q.y = 0.f; r.q.z = 0.f; r.q.w = 0.f;
+	if (!on) return;
+	const float* gt = (const float*)geoTab;
+	const float4* dq = *(const float4* const*)(geoTab + 12);
+	const int dw = ((const int*)(geoTab + 13))[0], dh = ((const int*)(geoTab + 13))[1];
+	float Tl[9], Tm[3];
+#pragma unroll
+	for (int i = 0; i < 9; ++i) Tl[i] = gt[i];
+#pragma unroll
+	for (int i = 0; i < 3; ++i) Tm[i] = gt[9 + i];
+	if (dq == nullptr) return;   // (after the tables: the pointer travels with them)
+	r.has = true;
+	const float Xc0 = (float)X0x * depth, Xc1 = (float)X0y * depth, Xc2 = depth;
+	const float Y0 = (Tl[0] * Xc0 + Tl[1] * Xc1 + Tl[2] * Xc2) + Tm[0];
+	const float Y1 = (Tl[3] * Xc0 + Tl[4] * Xc1 + Tl[5] * Xc2) + Tm[1];
+	const float Y2 = (Tl[6] * Xc0 + Tl[7] * Xc1 + Tl[8] * Xc2) + Tm[2];
+	r.Y2 = Y2;
+	if (Y2 > 0) {
+		const float x1x = Y0 / Y2, x1y = Y1 / Y2;
+		r.x1x = x1x; r.x1y = x1y;
+		if (pm_inside1(x1x, x1y, dw, dh)) {
+			r.ok = true;
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_GATHER_CENSUS)
+			pm_census::geoNote((int)x1x, (int)x1y, dw, dh);
+#endif
+#ifdef PM_PROBE_GEO_FIXED
+			// measurement builds only (profiles/geo_gather_bound.log): the map's first entry whatever the position -- wrong maps; what is measured is what the gather's
+			// cache misses and their latency cost the kernel, the most any rearrangement of it can give back
+			r.q = pm_loadq(pm_glob4(dq), 0u);
+#else
+			r.q = pm_loadq(pm_glob4(dq), pm_dq_index((int)x1x, (int)x1y, dw, dh));
+#endif
+			PM_GEO_HOLD();
+		}
+	}
+}
+
+// The term from the footprint on (DepthMap.cpp:540-550), one copy for both ways of fetching it: the four texels around (x1x, x1y) of the source view's depth map, the
+// point's depth Y2 there, the transforms back into the reference view.  TImage::sample with validity functor, Types.inl:2299-2314; IsDepthSimilar(z,d,0.03), Util.inl:798-809
+__device__ __forceinline__ float pm_geo_consistency(float x1x, float x1y, float Y2, float x0y0, float x1y0, float x0y1, float x1y1, const float* Tr, const float* Tn, int x, int y) {
+	float consistency = 4.f;
+	const int lx = (int)x1x, ly = (int)x1y;
+	const float fx = x1x - (float)lx, fx1 = 1.f - fx;
+	const float fy = x1y - (float)ly, fy1 = 1.f - fy;
+	const bool b00 = pm_fabsf(Y2 - x0y0) / Y2 < 0.03f, b10 = pm_fabsf(Y2 - x1y0) / Y2 < 0.03f;
+	const bool b01 = pm_fabsf(Y2 - x0y1) / Y2 < 0.03f, b11 = pm_fabsf(Y2 - x1y1) / Y2 < 0.03f;
+	if (b00 || b10 || b01 || b11) {
+		const float depth1 =
+			fy1 * (fx1 * (b00 ? x0y0 : (b10 ? x1y0 : (b01 ? x0y1 : x1y1))) + fx * (b10 ? x1y0 : (b00 ? x0y0 : (b11 ? x1y1 : x0y1)))) +
+			fy  * (fx1 * (b01 ? x0y1 : (b11 ? x1y1 : (b00 ? x0y0 : x1y0))) + fx * (b11 ? x1y1 : (b01 ? x0y1 : (b10 ? x1y0 : x0y0))));
+		const float Xd0 = x1x * depth1, Xd1 = x1y * depth1, Xd2 = depth1;
+		const float B0 = (Tr[0] * Xd0 + Tr[1] * Xd1 + Tr[2] * Xd2) + Tn[0];
+		const float B1 = (Tr[3] * Xd0 + Tr[4] * Xd1 + Tr[5] * Xd2) + Tn[1];
+		const float B2 = (Tr[6] * Xd0 + Tr[7] * Xd1 + Tr[8] * Xd2) + Tn[2];
+		const float xbx = B0 / B2, xby = B1 / B2;
+		const float dx = (float)x - xbx, dy = (float)y - xby;
+		const float dist = pm_sqrtf(dx * dx + dy * dy); // norm(Point2f) = SEACAVE::norm(TPoint2<float>): float (Types.inl:1021-1024); pinned by oracle/_ref
+		consistency = pm_minf(pm_sqrtf(dist * (dist + 2.f)), consistency);
+	}
+	return consistency;
+}
+
 // ScorePixelImage for this lane's source view, DepthMap.cpp:465-564.
 // sf0..3: the (view-independent) smoothness factors of the up-to-4 close neighbours, in insertion order; exactly 1.f for a neighbour that does not exist or does
 // not take part (DepthMap.cpp:524-533).
@@ -626,7 +766,8 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		int x, int y, double X0x, double X0y, float normSq0, float sumW, const float2* wts,
 		float depth, float nx, float ny, float nz,
 		float sf0, float sf1, float sf2, float sf3, float prior,
-		const double* hot, const double* geoTab, const PMImgBuf& rs PM_PROF_ARG, const double* rpre = nullptr, const float* sfp = nullptr)
+		const double* hot, const double* geoTab, const PMImgBuf& rs PM_PROF_ARG, const double* rpre = nullptr, const float* sfp = nullptr,
+		const PMGeoReq* greq = nullptr, int gsel = 0, int gn = 1)
 {
 	const int sw = ((const int*)(hot + 12))[0], sh = ((const int*)(hot + 12))[1];
 	float H[9];
@@ -734,52 +875,66 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 	score *= sf0; score *= sf1; score *= sf2; score *= sf3;
 	if (GEO) {
 		// geometric consistency, DepthMap.cpp:535-551
-		// the source view's depth-map pointer and its four transforms are requested together (they were five dependent round trips per evaluation)
+		if (!greq) {
+			// The init kernel and the speculative kernels keep the term as it was, on the row-major map: the source view's depth-map pointer and its four transforms are requested
+			// together (they were five dependent round trips per evaluation), then two 8-byte footprint rows.  The init kernel walks the reference view row by row, where the
+			// row-major map is the one whose neighbouring footprints share cache lines (it lost 5-8 % on the quad copy); the speculative kernels are bound by a visit's dependent
+			// chain and lost 0.3-0.5 % of the 13-view step with the 16-byte load in the same place (profiles/geo_gather_ab.log).
+			const float* gt = (const float*)geoTab;
+			const float* sdepth = *(const float* const*)(geoTab + 12);
+			const int dw = ((const int*)(geoTab + 13))[0], dh = ((const int*)(geoTab + 13))[1];
+			float Tl[9], Tm[3], Tr[9], Tn[3];
+#pragma unroll
+			for (int i = 0; i < 9; ++i) { Tl[i] = gt[i]; Tr[i] = gt[12 + i]; }
+#pragma unroll
+			for (int i = 0; i < 3; ++i) { Tm[i] = gt[9 + i]; Tn[i] = gt[21 + i]; }
+#pragma unroll
+			for (int i = 0; i < 9; ++i) PM_OPAQUE(Tr[i]);
+#pragma unroll
+			for (int i = 0; i < 3; ++i) PM_OPAQUE(Tn[i]);
+			if (sdepth != nullptr) {
+				float consistency = 4.f;
+				const float Xc0 = (float)X0x * depth, Xc1 = (float)X0y * depth, Xc2 = depth;
+				const float Y0 = (Tl[0] * Xc0 + Tl[1] * Xc1 + Tl[2] * Xc2) + Tm[0];
+				const float Y1 = (Tl[3] * Xc0 + Tl[4] * Xc1 + Tl[5] * Xc2) + Tm[1];
+				const float Y2 = (Tl[6] * Xc0 + Tl[7] * Xc1 + Tl[8] * Xc2) + Tm[2];
+				if (Y2 > 0) {
+					const float x1x = Y0 / Y2, x1y = Y1 / Y2;
+					if (pm_inside1(x1x, x1y, dw, dh)) {
+						const int lx = (int)x1x, ly = (int)x1y;
+						const pm_gcf p = pm_glob(sdepth) + (size_t)ly * dw + lx;
+						consistency = pm_geo_consistency(x1x, x1y, Y2, p[0], p[1], p[dw], p[dw + 1], Tr, Tn, x, y);
+					}
+				}
+				score += kp.geoWeight * consistency;
+			}
+		} else {
+		// pm_sweep2_kernel: the request -- transforms Tl / Tm, projection, the two quotients, inside test and the 16-byte load of the footprint from the quad copy -- was made
+		// for all of the lane's views at the head of the trip (pm_visit); the view of this round is picked here, where the term takes it
+		PMGeoReq rq = greq[0];
+#pragma unroll
+		for (int i = 1; i < gn; ++i) if (gsel == i) rq = greq[i];
 		const float* gt = (const float*)geoTab;
-		const float* sdepth = *(const float* const*)(geoTab + 12);
-		const int dw = ((const int*)(geoTab + 13))[0], dh = ((const int*)(geoTab + 13))[1];
-		float Tl[9], Tm[3], Tr[9], Tn[3];
+		float Tr[9], Tn[3];
 #pragma unroll
-		for (int i = 0; i < 9; ++i) { Tl[i] = gt[i]; Tr[i] = gt[12 + i]; }
+		for (int i = 0; i < 9; ++i) Tr[i] = gt[12 + i];
 #pragma unroll
-		for (int i = 0; i < 3; ++i) { Tm[i] = gt[9 + i]; Tn[i] = gt[21 + i]; }
+		for (int i = 0; i < 3; ++i) Tn[i] = gt[21 + i];
 #pragma unroll
 		for (int i = 0; i < 9; ++i) PM_OPAQUE(Tr[i]);
 #pragma unroll
 		for (int i = 0; i < 3; ++i) PM_OPAQUE(Tn[i]);
-		if (sdepth != nullptr) {
+		if (rq.has) {
 			float consistency = 4.f;
-			const float Xc0 = (float)X0x * depth, Xc1 = (float)X0y * depth, Xc2 = depth;
-			const float Y0 = (Tl[0] * Xc0 + Tl[1] * Xc1 + Tl[2] * Xc2) + Tm[0];
-			const float Y1 = (Tl[3] * Xc0 + Tl[4] * Xc1 + Tl[5] * Xc2) + Tm[1];
-			const float Y2 = (Tl[6] * Xc0 + Tl[7] * Xc1 + Tl[8] * Xc2) + Tm[2];
-			if (Y2 > 0) {
-				const float x1x = Y0 / Y2, x1y = Y1 / Y2;
-				if (pm_inside1(x1x, x1y, dw, dh)) {
-					// TImage::sample with validity functor, Types.inl:2299-2314; IsDepthSimilar(z,d,0.03), Util.inl:798-809
-					const int lx = (int)x1x, ly = (int)x1y;
-					const float fx = x1x - (float)lx, fx1 = 1.f - fx;
-					const float fy = x1y - (float)ly, fy1 = 1.f - fy;
-					const pm_gcf p = pm_glob(sdepth) + (size_t)ly * dw + lx;
-					const float x0y0 = p[0], x1y0 = p[1], x0y1 = p[dw], x1y1 = p[dw + 1];
-					const bool b00 = pm_fabsf(Y2 - x0y0) / Y2 < 0.03f, b10 = pm_fabsf(Y2 - x1y0) / Y2 < 0.03f;
-					const bool b01 = pm_fabsf(Y2 - x0y1) / Y2 < 0.03f, b11 = pm_fabsf(Y2 - x1y1) / Y2 < 0.03f;
-					if (b00 || b10 || b01 || b11) {
-						const float depth1 =
-							fy1 * (fx1 * (b00 ? x0y0 : (b10 ? x1y0 : (b01 ? x0y1 : x1y1))) + fx * (b10 ? x1y0 : (b00 ? x0y0 : (b11 ? x1y1 : x0y1)))) +
-							fy  * (fx1 * (b01 ? x0y1 : (b11 ? x1y1 : (b00 ? x0y0 : x1y0))) + fx * (b11 ? x1y1 : (b01 ? x0y1 : (b10 ? x1y0 : x0y0))));
-						const float Xd0 = x1x * depth1, Xd1 = x1y * depth1, Xd2 = depth1;
-						const float B0 = (Tr[0] * Xd0 + Tr[1] * Xd1 + Tr[2] * Xd2) + Tn[0];
-						const float B1 = (Tr[3] * Xd0 + Tr[4] * Xd1 + Tr[5] * Xd2) + Tn[1];
-						const float B2 = (Tr[6] * Xd0 + Tr[7] * Xd1 + Tr[8] * Xd2) + Tn[2];
-						const float xbx = B0 / B2, xby = B1 / B2;
-						const float dx = (float)x - xbx, dy = (float)y - xby;
-						const float dist = pm_sqrtf(dx * dx + dy * dy); // norm(Point2f) = SEACAVE::norm(TPoint2<float>): float (Types.inl:1021-1024); pinned by oracle/_ref
-						consistency = pm_minf(pm_sqrtf(dist * (dist + 2.f)), consistency);
-					}
+			const float Y2 = rq.Y2;
+			{
+				const float x1x = rq.x1x, x1y = rq.x1y;
+				if (rq.ok) {
+					consistency = pm_geo_consistency(x1x, x1y, Y2, rq.q.x, rq.q.y, rq.q.z, rq.q.w, Tr, Tn, x, y);
 				}
 			}
 			score += kp.geoWeight * consistency;
+		}
 		}
 	}
 	// low-resolution prior, DepthMap.cpp:553-561
@@ -1280,6 +1435,23 @@ __global__ void pm_nearest_up_f_kernel(const float* __restrict__ s, float* __res
 		const int x = (int)(i % dw), y = (int)(i / dw);
 		const int nx = pm_nn_index(x, dw, sw), ny = pm_nn_index(y, dh, sh);
 		d[i] = s[(size_t)ny * sw + nx];
+	}
+}
+
+// The quad copy of one source depth map (PMSrcView::dqBase, pm_dq_index): one thread per ENTRY, in the copy's own order, so the 16-byte writes of a wave are one run and
+// the reads walk an anti-diagonal of the row-major map (each texel is read by four entries; the cache serves three of them).  The values travel as their bit patterns.
+// Texels beyond the last column or row: 0 (entries no inside sample reads).
+struct alignas(16) PMQuadBits { uint32_t x, y, z, w; };
+__global__ void pm_depth_quads_kernel(const uint32_t* __restrict__ s, PMQuadBits* __restrict__ q, int dw, int dh) {
+	const size_t n = (size_t)dw * dh;
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+		const int r = (int)(i / (size_t)dh), ly = (int)(i - (size_t)r * dh);
+		int lx = (r - ly) % dw; if (lx < 0) lx += dw;      // the one column of row ly whose anti-diagonal folds onto row r of the copy
+		const size_t o = (size_t)ly * dw + lx;
+		const bool xin = lx + 1 < dw, yin = ly + 1 < dh;
+		PMQuadBits e;
+		e.x = s[o]; e.y = xin ? s[o + 1] : 0u; e.z = yin ? s[o + dw] : 0u; e.w = (xin && yin) ? s[o + dw + 1] : 0u;
+		q[i] = e;
 	}
 }
 

@@ -651,7 +651,7 @@ class PatchMatchHIP:
         self._chk(self._lib.pmhip_resize(self._h, kind, img, w, h, arg, o))
         return o
 
-    RESAMPLE_AREA, RESAMPLE_UPSAMPLE, RESAMPLE_NEAREST_DOWN, RESAMPLE_NEAREST_UP, RESAMPLE_MASK_LEVEL, RESAMPLE_SKEW, RESAMPLE_QUAD = range(7)
+    RESAMPLE_AREA, RESAMPLE_UPSAMPLE, RESAMPLE_NEAREST_DOWN, RESAMPLE_NEAREST_UP, RESAMPLE_MASK_LEVEL, RESAMPLE_SKEW, RESAMPLE_QUAD, RESAMPLE_DEPTH_QUADS = range(8)
 
     def resample(self, kind, src, src_size, dst, dst_size, arg=0, n_img=1):
         """pmhip_resample: one resampler of csrc/pm_kernels.hip through production's launch, `src_size` = (sw, sh) -> `dst_size` = (dw, dh).  `src` and `dst` are flat
@@ -662,7 +662,7 @@ class PatchMatchHIP:
         (sw, sh), (dw, dh) = src_size, dst_size
         ps, pd = sw * sh, dw * dh
         ns, nd = {self.RESAMPLE_UPSAMPLE: (4 * ps, 5 * pd), self.RESAMPLE_NEAREST_DOWN: (4 * ps, 4 * pd),
-                  self.RESAMPLE_QUAD: (ps * n_img, (dw + dh - 1) * dh * 4 * n_img)}.get(kind, (ps * n_img, pd * n_img))
+                  self.RESAMPLE_QUAD: (ps * n_img, (dw + dh - 1) * dh * 4 * n_img), self.RESAMPLE_DEPTH_QUADS: (ps, pd * 4)}.get(kind, (ps * n_img, pd * n_img))
         if not (isinstance(dst, np.ndarray) and dst.dtype == dt and dst.flags.c_contiguous and dst.flags.writeable and dst.size == nd):
             raise ValueError("resample: dst must be a writable C-contiguous %s array of %d elements" % (np.dtype(dt).name, nd))
         src = np.ascontiguousarray(src, dt)

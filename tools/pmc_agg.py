@@ -7,7 +7,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     key = (r["Dispatch_Id"], k)
     if key not in seen:
         seen.add(key); cnt[k] += 1
-for k in sorted(agg, key=lambda k: -sum(agg[k].values()))[:6]:
+for k in sorted(agg, key=lambda k: -sum(agg[k].values()))[:12]:
     print(k, "dispatches", cnt[k])
     for c, v in sorted(agg[k].items()):
         print("   %-28s sum %.4g  per-dispatch %.4g" % (c, v, v / max(1, cnt[k])))
