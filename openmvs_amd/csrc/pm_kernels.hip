@@ -399,6 +399,7 @@ struct Stat { unsigned long long loads = 0, lanes = 0, blocksVM = 0, blocksPM = 
 inline std::vector<Rec> recs;
 inline std::map<int, Stat> stats;
 inline unsigned long long wgLaunch = ~0ull; inline unsigned wgX = 0, wgY = 0; inline int wgWidth = 0, wgG = 4;
+inline int laneAs = -1;   // pm_sweep_widen_kernel (tools/gather_census.py --widen): the lane a record is filed under -- the candidate order's, lane = sub * PPW + pixel; the shipped order is the regrouped one there
 inline unsigned trips[64], curKey = 0, curRow = 0; inline bool armed = false;   // armed: inside a pm_score_view call of pm_visit (the init kernel gathers through pm_bufload5 too)
 inline unsigned blocksOfQuads(const std::array<unsigned, 64>& blk, unsigned long long on, unsigned long long* hist) {
 	unsigned total = 0;
@@ -436,9 +437,11 @@ inline void report() {
 	flush(); geoReport();
 	for (auto& kv : stats) {
 		const Stat& s = kv.second; const double L = (double)s.loads, Q = 16.0 * L;
-		fprintf(stderr, "gather census: level width %d: %llu tap wave-loads, %.1f active lanes per load; blocks per load: view-major (shipped) %.2f, pixel-major %.2f, ratio %.3f; "
-			"blocks per quad (shipped) %.3f; quads touching 0/1/2/3/4 blocks: %.1f %.1f %.1f %.1f %.1f %%\n", kv.first, s.loads, s.lanes / L, s.blocksVM / L, s.blocksPM / L,
-			(double)s.blocksVM / (double)s.blocksPM, s.blocksVM / Q, 100.0 * s.quadsVM[0] / Q, 100.0 * s.quadsVM[1] / Q, 100.0 * s.quadsVM[2] / Q, 100.0 * s.quadsVM[3] / Q, 100.0 * s.quadsVM[4] / Q);
+		const bool wn = wgG >= 16;   // the speculative kernel: the first column is the candidate order, the second the shipped one
+		fprintf(stderr, "gather census: level width %d: %llu tap wave-loads, %.1f active lanes per load; blocks per load: %s %.2f, %s %.2f, ratio %.3f; "
+			"blocks per quad (%s) %.3f; quads touching 0/1/2/3/4 blocks: %.1f %.1f %.1f %.1f %.1f %%\n", kv.first, s.loads, s.lanes / L,
+			wn ? "lanes of a pixel PPW apart (candidate)" : "view-major (shipped)", s.blocksVM / L, wn ? "lanes of a pixel adjacent (shipped)" : "pixel-major", s.blocksPM / L,
+			(double)s.blocksVM / (double)s.blocksPM, wn ? "candidate" : "shipped", s.blocksVM / Q, 100.0 * s.quadsVM[0] / Q, 100.0 * s.quadsVM[1] / Q, 100.0 * s.quadsVM[2] / Q, 100.0 * s.quadsVM[3] / Q, 100.0 * s.quadsVM[4] / Q);
 	}
 }
 inline void enter() {   // (fibers of one workgroup run to the end before the next workgroup starts: a change of workgroup closes the previous one's records)
@@ -447,8 +450,9 @@ inline void enter() {   // (fibers of one workgroup run to the end before the ne
 }
 inline void trip() { enter(); trips[threadIdx.x & 63]++; }
 inline void view(int width, int G, int u) { wgWidth = width; wgG = G; curKey = (trips[threadIdx.x & 63] * 8u + (unsigned)u) * 8u; curRow = 0; armed = true; }
-inline void viewEnd() { armed = false; }
-inline void note(unsigned i0, unsigned i1, unsigned i2, unsigned i3, unsigned i4) { if (armed) recs.push_back(Rec{curKey + curRow++, threadIdx.x & 63u, {i0, i1, i2, i3, i4}}); }
+inline void viewAs(int width, int G, int u, int lane) { view(width, G, u); laneAs = lane; }
+inline void viewEnd() { armed = false; laneAs = -1; }
+inline void note(unsigned i0, unsigned i1, unsigned i2, unsigned i3, unsigned i4) { if (armed) recs.push_back(Rec{curKey + curRow++, laneAs >= 0 ? (unsigned)laneAs : threadIdx.x & 63u, {i0, i1, i2, i3, i4}}); }
 // The geometric term's gather (pm_geo_request): per lane row of a wave-load of pm_sweep2_kernel -- one (trip, source view): PPW pixels -- the 64-byte blocks its active lanes touch under the parent's
 // layout (row-major floats, two 8-byte loads on two rows) and under the three candidate orders of the quad copy; tools/gather_census.py --geo, profiles/geo_gather_census.txt.
 struct GeoRec { unsigned key, lane; int vw, lx, ly, dw, dh; };
@@ -488,6 +492,7 @@ inline void geoNote(int lx, int ly, int dw, int dh) { if (geoVw >= 0) geoRecs.pu
 #define PM_CENSUS_GEO(vw) pm_census::geoView(vw)
 #define PM_CENSUS_TRIP() pm_census::trip()
 #define PM_CENSUS_VIEW(width, G, u) pm_census::view((width), (G), (u))
+#define PM_CENSUS_VIEW_AS(width, G, u, lane) pm_census::viewAs((width), (G), (u), (lane))
 #define PM_CENSUS_VIEW_END() pm_census::viewEnd()
 #endif
 __device__ __forceinline__ void pm_bufload5(pm_f4v& q0, pm_f4v& q1, pm_f4v& q2, pm_f4v& q3, pm_f4v& q4, unsigned i0, unsigned i1, unsigned i2, unsigned i3, unsigned i4, pm_rsrc r) {
@@ -505,10 +510,17 @@ __device__ __forceinline__ unsigned pm_mad24(int a, int b, unsigned c) { return 
 #define PM_CENSUS_TRIP()
 #define PM_CENSUS_GEO(vw)
 #define PM_CENSUS_VIEW(width, G, u)
+#define PM_CENSUS_VIEW_AS(width, G, u, lane)
 #define PM_CENSUS_VIEW_END()
 #endif
 // what the buffer path of the tap rows needs, wave-uniform: the descriptor of the level's quad buffer
+#ifdef PM_PROBE_WIDEN_QUAD_BLOCK
+// measurement builds only (profiles/widen_lane_order_bound.log): the kernel that sets oneBlock gathers every hardware quad's four entries of a tap wave-load from ONE 64-byte
+// block -- lane 0's block, each lane its own entry of it -- for one v_mov_dpp + v_bfi per tap: wrong maps; what is measured is the most any lane order can give the gather
+struct PMImgBuf { pm_rsrc rs; bool oneBlock = false; };
+#else
 struct PMImgBuf { pm_rsrc rs; };
+#endif
 __device__ __forceinline__ PMImgBuf pm_make_imgbuf(const PMTask& t) {
 	PMImgBuf b;
 	b.rs = pm_make_rsrc(t.qArr, t.qCount);
@@ -595,6 +607,12 @@ __device__ __forceinline__ void pm_row_issue(const PMImgBuf& rs, unsigned qbase,
 		if (CORNERS && (j == 0 || j == 4)) pm_range_corner(rg, p.ptx[j], p.pty[j], X2);
 		X0 += h0; X1 += h3; X2 += h6;
 	}
+#if defined(PM_PROBE_WIDEN_QUAD_BLOCK) && defined(__HIP_DEVICE_COMPILE__)
+	if (BUF && rs.oneBlock) {
+#pragma unroll
+		for (int j = 0; j < 5; ++j) idx[j] = (idx[j] & 3u) | ((unsigned)__builtin_amdgcn_update_dpp((int)idx[j], (int)idx[j], 0x00, 0xf, 0xf, false) & ~3u);   // quad_perm [0,0,0,0]
+	}
+#endif
 	if (BUF) pm_bufload5(q.q0, q.q1, q.q2, q.q3, q.q4, idx[0], idx[1], idx[2], idx[3], idx[4], rs.rs);
 	else { q.q0 = pm_loadq(imgQ, idx[0]); q.q1 = pm_loadq(imgQ, idx[1]); q.q2 = pm_loadq(imgQ, idx[2]); q.q3 = pm_loadq(imgQ, idx[3]); q.q4 = pm_loadq(imgQ, idx[4]); }
 }

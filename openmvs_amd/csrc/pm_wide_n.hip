@@ -18,6 +18,17 @@
 // Differences from pm_sweep_wide_kernel, all forced by several pixels sharing a wave: a pixel that is masked / done does not leave (its lanes idle to the end of
 // the wave's loop); every cross-lane read (the other groups' scores and planes) is done by all lanes before the per-pixel replay, never inside its
 // data-dependent control flow; window-less tap rows only (the quad images).
+//
+// Lane order: a pixel's lanes are contiguous (p = lane / LPP, v = lane & 7), so a hardware quad is one pixel's four source views and every tap wave-load sends a quad to
+// four images.  The order pm_sweep2_kernel took (a pixel's lanes PPW apart: a quad = four neighbouring diagonal pixels on one view) was bounded, counted, built and measured
+// here and is NOT taken.  Bound (measurement build -DPM_PROBE_WIDEN_QUAD_BLOCK, every quad gathers from one 64-byte block): 72.9 -> 66.8 us per photometric launch at 100
+// views (-8.4 %), 81.6 -> 72.6 geometric (-11 %), nothing at 13 views.  Census (tools/gather_census.py --widen): 1.6-1.7 blocks per quad instead of 4.  Built
+// (profiles/widen_lane_order_experiment.diff: head words spread over the pixel's lanes and published in LDS, factors through LDS, the reduction by row rotations and one
+// v_permlane16_swap; bit-identical, 167-168 VGPRs, no scratch, 3.2 KB of LDS): with the same workgroup map 69.2 against 68.8 us photometric and 75.7 against 75.3 geometric at
+// 100 views, 40.8 against 40.2 and 46.5 against 46.0 at 13 -- slower everywhere; the 13-view step lost 1.6 % on its own.  What the quad saves in the address unit the visit
+// pays in its dependent chain.
+// Workgroup map: XCD-aware as pm_sweep2_kernel's (below), measured on its own: 73.6 -> 68.8 us photometric, 82.0 -> 75.3 geometric at 100 views, 41.5 -> 40.2 and
+// 48.5 -> 46.0 at 13 (profiles/widen_lane_order_kernel_stats_*.csv); the benchmark's steps in profiles/widen_lane_order_ab.log.
 #pragma once
 #include "pm_kernels.hip"
 
@@ -32,13 +43,26 @@ __global__ __launch_bounds__(64, PM_WIDEN_MINWAVES) void pm_sweep_widen_kernel(c
 	PM_PROF_DECL;
 	__shared__ float2 s_w[PPW][PM_NT + 1];
 	__shared__ double s_src[G * NBD];
-	const PMTask& t = tasks[blockIdx.y];
+	// XCD-aware block mapping as in pm_sweep2_kernel: contiguous (view, chunk) ranges per XCD, so that neighbouring chunks of a view's diagonal -- whose patches overlap in
+	// every source image -- share one L2 instead of landing on eight (the hardware deals workgroups round-robin to the XCDs); DESIGN.md 4.2, profiles/widen_lane_order_ab.log
+	unsigned vbx = blockIdx.x, vby = blockIdx.y;
+	{
+		const unsigned nbx = gridDim.x, nwg = nbx * gridDim.y, orig = blockIdx.y * nbx + blockIdx.x;
+		const unsigned xcd = orig % 8u, q = nwg / 8u, r = nwg % 8u;
+		const unsigned wgid = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + orig / 8u;
+		vby = wgid / nbx; vbx = wgid - vby * nbx;
+	}
+	const PMTask& t = tasks[vby];
+#ifdef PM_PROBE_WIDEN_QUAD_BLOCK
+	PMImgBuf rs = pm_make_imgbuf(t); rs.oneBlock = true;
+#else
 	const PMImgBuf rs = pm_make_imgbuf(t);
+#endif
 	const int lane = threadIdx.x, p = lane / LPP, sub = lane % LPP, c = sub >> 3, v = lane & 7, seg = p * LPP;
 	for (int i = lane; i < G * NBD; i += 64) s_src[i] = ((const double*)&t.src[i / NBD])[i % NBD];
 	const double* hot = s_src + v * NBD;
 	const int w = t.w, h = t.h;
-	const PMStepPix sp = pm_step_pixel<TILED>(st, w, h, (int)blockIdx.x * PPW + p);
+	const PMStepPix sp = pm_step_pixel<TILED>(st, w, h, (int)vbx * PPW + p);
 	const bool active = sp.active;
 	const int x = sp.x, y = sp.y;                                 // a segment without a pixel takes the map's first one and never writes
 	const size_t idx = (size_t)y * w + x;
@@ -109,6 +133,7 @@ __global__ __launch_bounds__(64, PM_WIDEN_MINWAVES) void pm_sweep_widen_kernel(c
 	PM_TICK(0); PM_COUNT(9, 1);
 	while (__any(stage != W_DONE)) {
 		const bool on = stage != W_DONE;                           // (uniform inside a pixel's segment)
+		PM_CENSUS_TRIP();
 		// what the stage after the propagation candidates would be if they change nothing: RefineIters: (DepthMap.cpp:802-827) on the current state
 		int specStage = W_REFINE; unsigned specIdx = idxScale; bool specSmooth = smooth;
 		float specScale = scaleRange, specRange = depthRange, specP0 = p0, specP1 = p1;
@@ -194,9 +219,12 @@ __global__ __launch_bounds__(64, PM_WIDEN_MINWAVES) void pm_sweep_widen_kernel(c
 		}
 		PM_TICK(2);
 		float sc = PM_INF;
-		if (need && v < t.nSrc)
+		if (need && v < t.nSrc) {
+			PM_CENSUS_VIEW_AS(t.w, LPP, 0, sub * PPW + p);
 			sc = pm_score_view<GEO, BUF ? 2 : 1, true>(t.src[v], t, kp, x, y, X0x, X0y, normSq0, sumW, s_w[p], hd, hnx, hny, hnz, sf[0], sf[1], sf[2], sf[3], 0.f,
 				hot, hot + PM_SRC_HOT, rs PM_PROF_PASS);
+			PM_CENSUS_VIEW_END();
+		}
 		const float nconf = pm_aggregate<G>(sc, t.nSrc, kp.thRobust);
 		// ---- what the NH groups of my pixel found: read by every lane, outside any per-pixel control flow ----
 		bool gNeed[NH]; float gConf_[NH], gD[NH], gNx[NH], gNy[NH], gNz[NH], gP0[NH], gP1[NH];
