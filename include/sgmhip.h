@@ -122,7 +122,12 @@ typedef struct SGMHipStats { double costMs, aggrMs, wtaMs; uint64_t calls, aggrL
 /* The tSGM coarse-to-fine loop of SemiGlobalMatcher::Match(scene, ...) (libs/MVS/SemiGlobalMatcher.cpp:577-706) for one rectified pair in one call, resident
  * on the device: per level the image pyramids (INTER_AREA from the full-resolution images), FlipDirection + Disparity2RangeMap, Match right->left and
  * left->right, ConsistencyCrossCheck; on the first level also filterSpeckles(nSpeckleSize, 5) and ExtractMask; finally RefineDisparityMap.  Equal to driving the
- * single steps above as openmvs_amd/tsgm.py does.  Images: w x h (a multiple of 2^levels), BGR 8-bit and gray float of the rectified pair, their 8-bit validity
+ * single steps above as openmvs_amd/tsgm.py does.
+ * minResolution == 0 is plain SGM (:585-590, 643-706), one level at full resolution and *numLevels = 1: initLeftDisparity (size (round(w/2)-6) x (round(h/2)-6);
+ * NULL = all NO_DISP, the range [-18, 14)) only gives the global range of sgmhip_plain_range (sgmhip_plain.h); Match right->left runs with that range as it
+ * is, Match left->right with its negation (the reference's assignment, the opposite of the tSGM branch); then both cross-checks, both speckle filters and RefineDisparityMap.  No size-multiple
+ * rule applies.  An empty seed grid, or a range of <= 0 or more than SGMHIP_MAX_UNIFORM_DISP disparities, is SGMHIP_E_ARG; the text names the seed's min, max and D.
+ * Images: w x h (a multiple of 2^levels), BGR 8-bit and gray float of the rectified pair, their 8-bit validity
  * masks (Image::StereoRectifyImages); initLeftDisparity: nullable, the half-resolution map of the first level (Depth2DisparityMap of the sparse-point depth map,
  * :608-625), size (round(w_l/2)-6) x (round(h_l/2)-6) with w_l, h_l the coarsest level's size.  Outputs on the valid grid (w-6) x (h-6). */
 int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* rightBGR, const float* leftGray, const float* rightGray,
@@ -159,4 +164,5 @@ int sgmhip_stats_get(sgmhip_engine* e, SGMHipStats* out);
 #ifdef __cplusplus
 }
 #endif
+#include "sgmhip_plain.h"
 #endif /* SGMHIP_H_ */

@@ -2,6 +2,7 @@
 #include "../../include/sgmhip.h"
 #include "sgm_kernels.hip"
 #include "sgm_kernels_sub.hip"
+#include "sgm_kernels_wide.hip"
 #include "sgm_post.hip"
 #include "sgm_tsgm.hip"
 #include "sgm_rectify.hip"
@@ -26,6 +27,7 @@ struct sgmhip_engine : SGMProblemBufs {
 	DevBuf<unsigned short> d_P2s;
 	bool statsOn = false; SGMHipStats stats{};
 	DevBuf<unsigned char> d_deltas; size_t capDeltas = 0; int maxP2 = 65535;   // DELTA aggregation (uniform ranges, max P2 <= 255): 8 byte volumes instead of atomic u16 sums
+	bool uniformEntry = false;    // the problem came as two integers (sgmhip_set_problem_uniform, the plain loop): 129 .. 256 disparities aggregate with sgm_path_wide_kernel<4> too
 	bool uniform = false; int uniformMin = 0, uniformMax = 0; DevBuf<SGMUniform> d_uniform;   // every pixel has [uniformMin, uniformMax) and idx = pixel * nD (checked on the device at set_problem): the register-resident path kernel applies
 	int subGroups = 0;            // 0, or the lanes per sub-group (8, 16, 32): Match with the sub-group kernels of sgm_kernels_sub.hip (narrow, ragged ranges); see sgmhip_set_sub_group_kernels
 	struct Ev { hipEvent_t a, b; int kind; }; std::vector<Ev> events;
@@ -63,7 +65,7 @@ static int sgmReserve(sgmhip_engine* e, int w, int h, uint64_t numCosts, int max
 		e->capImg = cI; e->capPix = cP; e->capCosts = cC;
 	}
 	e->w = w; e->h = h; e->vw = w - 2 * SGM_HW; e->vh = h - 2 * SGM_HW; e->numCosts = numCosts; e->maxNumDisp = maxNumDisp;
-	e->uniform = false;
+	e->uniform = false; e->uniformEntry = false;
 	return 0;
 }
 
@@ -115,6 +117,50 @@ int sgmhip_set_problem(sgmhip_engine* e, const uint8_t* leftBGR, const float* le
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	e->uniform = hu.ok != 0 && hu.maxDisp - hu.minDisp == maxNumDisp && (uint64_t)nPix * (uint64_t)maxNumDisp == numCosts;
 	e->uniformMin = hu.minDisp; e->uniformMax = hu.maxDisp;
+	return 0;
+}
+
+// the resident problem becomes the uniform one of [minDisp, maxDisp): buffers for w x h and its pixels * D costs, the pixel table filled on the device (asynchronous;
+// the images are the caller's to copy in).  An error leaves no problem resident.
+static int sgmReserveUniform(sgmhip_engine* e, int w, int h, int minDisp, int maxDisp) {
+	const int D = maxDisp - minDisp;
+	const size_t nPix = (size_t)(w - 2 * SGM_HW) * (h - 2 * SGM_HW);
+	const int rc = sgmReserve(e, w, h, (uint64_t)nPix * (uint64_t)D, D);
+	if (rc) { e->numCosts = 0; (void)hipGetLastError(); return rc; }
+	hipLaunchKernelGGL(sgm_fill_uniform_table_kernel, dim3((unsigned)std::min<size_t>((nPix + 255) / 256, 65535)), dim3(256), 0, e->stream, e->d_pixels.p, (long)nPix, minDisp, maxDisp);
+	e->uniform = true; e->uniformEntry = true; e->uniformMin = minDisp; e->uniformMax = maxDisp;
+	return 0;
+}
+// why [minDisp, maxDisp) cannot be a uniform problem ("" if it can): the text every entry point reports
+static std::string sgmUniformRefusal(long long minDisp, long long maxDisp) {
+	const long long D = maxDisp - minDisp;
+	if (D < 1 || D > SGMHIP_MAX_UNIFORM_DISP) return "a uniform range of " + std::to_string(D) + " disparities: it must hold 1 .. " + std::to_string(SGMHIP_MAX_UNIFORM_DISP) + " (SGMHIP_MAX_UNIFORM_DISP)";
+	if (minDisp < -32767 || maxDisp > 32767) return "a uniform range [" + std::to_string(minDisp) + ", " + std::to_string(maxDisp) + ") leaves int16 (or its negation does)";
+	return "";
+}
+
+int sgmhip_set_problem_uniform(sgmhip_engine* e, const uint8_t* leftBGR, const float* leftGray, const float* rightGray, int w, int h, int minDisp, int maxDisp) {
+	if (!e) return SGMHIP_E_ARG;
+	if (!leftBGR || !leftGray || !rightGray || w <= 2 * SGM_HW || h <= 2 * SGM_HW) { e->err = "set_problem_uniform: null image, or an image no larger than the 7x7 window"; return SGMHIP_E_ARG; }
+	{ const std::string why = sgmUniformRefusal(minDisp, maxDisp); if (!why.empty()) { e->err = "set_problem_uniform: " + why; return SGMHIP_E_ARG; } }
+	SGMCHK(e, hipSetDevice(e->device));
+	const size_t nImg = (size_t)w * h;
+	{ const int rc = sgmReserveUniform(e, w, h, minDisp, maxDisp); if (rc) return rc; }
+	SGMCHK(e, hipMemcpyAsync(e->d_color, leftBGR, nImg * 3, hipMemcpyHostToDevice, e->stream));
+	SGMCHK(e, hipMemcpyAsync(e->d_grayL, leftGray, nImg * 4, hipMemcpyHostToDevice, e->stream));
+	SGMCHK(e, hipMemcpyAsync(e->d_grayR, rightGray, nImg * 4, hipMemcpyHostToDevice, e->stream));
+	SGMCHK(e, hipStreamSynchronize(e->stream));                       // the images are the caller's memory
+	return 0;
+}
+
+int sgmhip_plain_range(const int16_t* seed, size_t n, int16_t* minDisp, int16_t* maxDisp) {
+	if (!seed || n == 0 || !minDisp || !maxDisp) return SGMHIP_E_ARG;
+	int16_t mn = seed[0], mx = seed[0];
+	for (size_t i = 1; i < n; ++i) { mn = std::min(mn, seed[i]); mx = std::max(mx, seed[i]); }
+	// every intermediate is a Disparity (:645-661): the conversions wrap
+	const int16_t numDisp = (int16_t)((int16_t)(mx - mn) + 16);
+	const int16_t disp = (int16_t)(mn + mx);
+	*minDisp = (int16_t)(disp - numDisp); *maxDisp = (int16_t)(disp + numDisp);
 	return 0;
 }
 
@@ -199,12 +245,25 @@ static void sgmLaunchPaths(sgmhip_engine* e, int P1, const SGMDirs& sd, int tota
 #undef SGM_RAGGED
 #undef SGM_PATH_TAIL
 }
+// the path kernel of a uniform range of more than 256 disparities (sgm_kernels_wide.hip): 8 entries per lane up to 512, 16 beyond; 4 for the 129 .. 256 of a problem
+// stated as two integers, where sgm_path_kernel<4> would serve (measured at 2048x1536, D = 256: profiles/plain_sgm_bench.log)
+template <bool DL>
+static void sgmLaunchPathsWide(sgmhip_engine* e, int P1, const SGMDirs& sd, int total) {
+	const int D = e->maxNumDisp;
+#define SGM_WIDE(NK_, A_) hipLaunchKernelGGL((sgm_path_wide_kernel<NK_, A_, DL>), dim3(total), dim3(64), 0, e->stream, e->d_grayL, e->w, e->vw, e->vh, D, \
+		e->d_costs, (unsigned*)e->d_accums.p, e->d_P2s, P1, sd, e->d_deltas, (unsigned long long)e->numCosts)
+#define SGM_WIDE_A(NK_) do { if (D % 4 == 0) SGM_WIDE(NK_, 4); else if (D % 2 == 0) SGM_WIDE(NK_, 2); else SGM_WIDE(NK_, 1); } while (0)
+	if (D <= 256) SGM_WIDE_A(4); else if (D <= 512) SGM_WIDE_A(8); else SGM_WIDE_A(16);
+#undef SGM_WIDE_A
+#undef SGM_WIDE
+}
 } // extern "C++"
 
 // cost volume, 8-path aggregation and winner-take-all of the resident problem (P2s already on the device: sgmSetP2s), asynchronous on the engine's stream.
 // Two mappings of work to lanes: one wavefront per line (subGroups == 0), or sub-groups of subGroups lanes per line and per pixel (sgm_kernels_sub.hip)
 static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
-	const int W = e->vw, H = e->vh, LP = e->subGroups;
+	const bool wide = e->maxNumDisp > 256;                           // only a uniform range gets here (sgmhip_set_problem_uniform): one wavefront per line, whatever subGroups says
+	const int W = e->vw, H = e->vh, LP = wide ? 0 : e->subGroups;
 	const long nPix = (long)W * H;
 	// cost volume: one pixel per lane, 64-pixel tiles of a row per wave -- it serves the narrow ranges of the sub-group mapping too (0.9 against 1.28 ms of a
 	// sub-group per pixel pair for 3-12 disparities per pixel at 2048x1536).  One range for all pixels (wide mapping): the right-image strip of a tile sits in LDS
@@ -212,7 +271,8 @@ static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
 	{
 		const long nTiles = (long)((W + 63) / 64) * H;
 		const dim3 g((unsigned)((nTiles + 3) / 4));
-		if (e->uniform && !LP) {
+		if (wide) hipLaunchKernelGGL(sgm_cost_uni_wide_kernel, g, dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->uniformMin, e->maxNumDisp, e->d_costs);
+		else if (e->uniform && !LP) {
 #define SGM_LAUNCH_UNI(MD_) hipLaunchKernelGGL((sgm_cost_uni_kernel<MD_>), g, dim3(256), 0, e->stream, e->d_color, e->d_grayL, e->d_grayR, e->w, e->h, W, H, e->uniformMin, e->maxNumDisp, e->d_costs)
 			if (e->maxNumDisp <= 64) SGM_LAUNCH_UNI(64); else if (e->maxNumDisp <= 128) SGM_LAUNCH_UNI(128); else SGM_LAUNCH_UNI(256);
 #undef SGM_LAUNCH_UNI
@@ -225,7 +285,8 @@ static int sgmMatch(sgmhip_engine* e, uint16_t P1) {
 	SGMDirs sd;
 	const int total = sgmSchedule(W, H, LP ? 64 / LP : 1, sd);
 	evB(e, 1);
-	if (total > 0) { if (delta) sgmLaunchPaths<true>(e, (int)P1, sd, total); else sgmLaunchPaths<false>(e, (int)P1, sd, total); }
+	if (total > 0 && (wide || (e->uniformEntry && !LP && e->maxNumDisp > 128))) { if (delta) sgmLaunchPathsWide<true>(e, (int)P1, sd, total); else sgmLaunchPathsWide<false>(e, (int)P1, sd, total); }
+	else if (total > 0) { if (delta) sgmLaunchPaths<true>(e, (int)P1, sd, total); else sgmLaunchPaths<false>(e, (int)P1, sd, total); }
 	if (e->statsOn) e->stats.aggrLaunches += 1;
 	evE(e);
 	evB(e, 2);
@@ -562,10 +623,9 @@ int tsgmLevels(int w, int h, unsigned minResolution) {
 inline int cvRound(double v) { return (int)nearbyint(v); }      // cv::saturate_cast<int>(double): round half to even
 }
 
-// the size rules of the loop: -> levels k (>= 1), or 0 with the engine's error text set
+// the size rules of the coarse-to-fine loop (minResolution > 0; 0 is tsgmPlainRun): -> levels k (>= 1), or 0 with the engine's error text set
 static int tsgmCheckSize(sgmhip_engine* e, int w, int h, unsigned minResolution) {
 	const int k = tsgmLevels(w, h, minResolution);
-	if (k == 0) { e->err = "plain SGM (minResolution = 0) is not driven here: only tSGM"; return 0; }
 	if ((w % (1 << k)) || (h % (1 << k)) || (w >> k) <= 2 * SGM_HW + 2 || (h >> k) <= 2 * SGM_HW + 2) { e->err = "image size must be a multiple of 2^levels and its coarsest level larger than the window"; return 0; }
 	return k;
 }
@@ -677,17 +737,67 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 	return 0;
 }
 
+// plain SGM (minResolution == 0, :585-590, 643-706) on a rectified pair that is on the device: one level at full resolution.  The seed only gives the global range
+// (sgmhip_plain_range); Match(right, left) runs with it as it is and Match(left, right) with its negation -- the reference's assignment, the opposite of the
+// tSGM branch (SetStereoRectificationROI centres the shared points' disparities around zero).  Then the first-level filtering and the refinement on the sums of the
+// left Match.  The masks are only cropped and re-extracted by the reference (:612-617, 705-706) and never read again: they are not computed.
+static int tsgmPlainRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned char* fRB, const float* fLG, const float* fRG, int w, int h,
+		const int16_t* initLeftDisparity, int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256],
+		int16_t* disparity, uint16_t* cost, int* numLevels) {
+	const int dW = cvRound(w * 0.5) - 2 * SGM_HW, dH = cvRound(h * 0.5) - 2 * SGM_HW;   // the seed: Image8U::computeResize(size, 0.5), :611-625
+	if (w <= 2 * SGM_HW || h <= 2 * SGM_HW || dW <= 0 || dH <= 0) { e->err = "plain SGM: the half-resolution seed grid of a " + std::to_string(w) + " x " + std::to_string(h) + " image is empty"; return SGMHIP_E_ARG; }
+	int16_t sMin = SGMP_NO_DISP, sMax = SGMP_NO_DISP, mn = 0, mx = 0;
+	if (initLeftDisparity) { const auto mm = std::minmax_element(initLeftDisparity, initLeftDisparity + (size_t)dW * dH); sMin = *mm.first; sMax = *mm.second; }
+	{ const int16_t two[2] = {sMin, sMax}; sgmhip_plain_range(two, 2, &mn, &mx); }
+	{ const std::string why = sgmUniformRefusal(mn, mx); if (!why.empty()) { e->err = "plain SGM: the seed's disparities span " + std::to_string(sMin) + " .. " + std::to_string(sMax) + " (min, max), which gives D = " + std::to_string((int)mx - (int)mn) + ": " + why; return SGMHIP_E_ARG; } }
+	hipStream_t st = e->stream;
+	const int vw = w - 2 * SGM_HW, vh = h - 2 * SGM_HW;
+	const size_t nImg = (size_t)w * h, nV = (size_t)vw * vh;
+	DevBuf<int16_t> lD, rD; DevBuf<int> par, siz;
+	SGMCHK(e, lD.alloc(nV)); SGMCHK(e, rD.alloc(nV)); SGMCHK(e, par.alloc(nV)); SGMCHK(e, siz.alloc(nV));
+	{ const int rc = sgmSetP2s(e, P1, P2s); if (rc) return rc; }
+	auto match = [&](const unsigned char* bgr, const float* gA, const float* gB, int a, int b, int16_t* out) -> int {
+		{ const int rc = sgmReserveUniform(e, w, h, a, b); if (rc) return rc; }
+		SGMCHK(e, hipMemcpyAsync(e->d_color, bgr, nImg * 3, hipMemcpyDeviceToDevice, st));
+		SGMCHK(e, hipMemcpyAsync(e->d_grayL, gA, nImg * 4, hipMemcpyDeviceToDevice, st));
+		SGMCHK(e, hipMemcpyAsync(e->d_grayR, gB, nImg * 4, hipMemcpyDeviceToDevice, st));
+		{ const int rc = sgmMatch(e, P1); if (rc) return rc; }
+		SGMCHK(e, hipMemcpyAsync(out, e->d_disp, nV * 2, hipMemcpyDeviceToDevice, st));
+		return 0;
+	};
+	{ const int rc = match(fRB, fRG, fLG, mn, mx, rD); if (rc) return rc; }          // :667-676
+	{ const int rc = match(fLB, fLG, fRG, -mx, -mn, lD); if (rc) return rc; }        // :678-685
+	hipLaunchKernelGGL(sgmp_cross_check_kernel, dim3(gridFor(nV)), dim3(256), 0, st, lD.p, (const int16_t*)rD.p, vw, vw, vh, 1);   // :698-706
+	hipLaunchKernelGGL(sgmp_cross_check_kernel, dim3(gridFor(nV)), dim3(256), 0, st, rD.p, (const int16_t*)lD.p, vw, vw, vh, 1);
+	sgmSpeckles(st, lD, vw, vh, nSpeckleSize, 5, par, siz); sgmSpeckles(st, rD, vw, vh, nSpeckleSize, 5, par, siz);
+	SGMCHK(e, hipMemcpyAsync(e->d_disp, lD, nV * 2, hipMemcpyDeviceToDevice, st));
+	if (subpixelSteps > 1)
+		hipLaunchKernelGGL(sgmp_refine_kernel, dim3(gridFor(nV)), dim3(256), 0, st, e->d_pixels, e->d_accums, (long)nV, e->d_disp, subpixelMode, subpixelSteps);
+	SGMCHK(e, hipGetLastError());
+	SGMCHK(e, hipMemcpyAsync(disparity, e->d_disp, nV * 2, hipMemcpyDeviceToHost, st));
+	SGMCHK(e, hipMemcpyAsync(cost, e->d_cost, nV * 2, hipMemcpyDeviceToHost, st));
+	SGMCHK(e, hipStreamSynchronize(st));
+	if (numLevels) *numLevels = 1;
+	return 0;
+}
+
 int sgmhip_tsgm_match(sgmhip_engine* e, const uint8_t* leftBGR, const uint8_t* rightBGR, const float* leftGray, const float* rightGray,
 		const uint8_t* leftMask, const uint8_t* rightMask, int w, int h, unsigned minResolution, const int16_t* initLeftDisparity,
 		int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels) {
 	if (!e || !leftBGR || !rightBGR || !leftGray || !rightGray || !leftMask || !rightMask || !P2s || !disparity || !cost || w <= 0 || h <= 0 || nSpeckleSize < 0 ||
 	    subpixelMode < 0 || subpixelMode > SGMP_SUBPIXEL_LC_BLEND || subpixelSteps < 0 || subpixelSteps > 64) return SGMHIP_E_ARG;
-	const int k = tsgmCheckSize(e, w, h, minResolution);
-	if (k == 0) return SGMHIP_E_ARG;
+	const int k = minResolution ? tsgmCheckSize(e, w, h, minResolution) : 0;
+	if (minResolution && k == 0) return SGMHIP_E_ARG;
 	SGMCHK(e, hipSetDevice(e->device));
 	hipStream_t st = e->stream;
 	const size_t nFull = (size_t)w * h;
 	DevBuf<unsigned char> fLB, fRB, fLM, fRM; DevBuf<float> fLG, fRG;          // the full-resolution inputs
+	if (!minResolution) {                                                      // plain SGM reads no mask
+		SGMCHK(e, fLB.alloc(nFull * 3)); SGMCHK(e, fRB.alloc(nFull * 3)); SGMCHK(e, fLG.alloc(nFull)); SGMCHK(e, fRG.alloc(nFull));
+		SGMCHK(e, hipMemcpyAsync(fLB, leftBGR, nFull * 3, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRB, rightBGR, nFull * 3, hipMemcpyHostToDevice, st));
+		SGMCHK(e, hipMemcpyAsync(fLG, leftGray, nFull * 4, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRG, rightGray, nFull * 4, hipMemcpyHostToDevice, st));
+		return tsgmPlainRun(e, fLB, fRB, fLG, fRG, w, h, initLeftDisparity, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
+	}
 	SGMCHK(e, fLB.alloc(nFull * 3)); SGMCHK(e, fRB.alloc(nFull * 3)); SGMCHK(e, fLG.alloc(nFull)); SGMCHK(e, fRG.alloc(nFull)); SGMCHK(e, fLM.alloc(nFull)); SGMCHK(e, fRM.alloc(nFull));
 	SGMCHK(e, hipMemcpyAsync(fLB, leftBGR, nFull * 3, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRB, rightBGR, nFull * 3, hipMemcpyHostToDevice, st));
 	SGMCHK(e, hipMemcpyAsync(fLG, leftGray, nFull * 4, hipMemcpyHostToDevice, st)); SGMCHK(e, hipMemcpyAsync(fRG, rightGray, nFull * 4, hipMemcpyHostToDevice, st));
@@ -783,9 +893,11 @@ int sgmhip_tsgm_match_rectified(sgmhip_engine* e, unsigned minResolution, const 
 	if (!e) return SGMHIP_E_ARG;
 	if (!P2s || !disparity || !cost || nSpeckleSize < 0 || subpixelMode < 0 || subpixelMode > SGMP_SUBPIXEL_LC_BLEND || subpixelSteps < 0 || subpixelSteps > 64) { e->err = "tsgm_match_rectified: null pointer or option out of range"; return SGMHIP_E_ARG; }
 	if (!e->rectW) { e->err = "no rectified pair is resident: call sgmhip_rectify_pair first"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	if (!minResolution) return tsgmPlainRun(e, e->d_rectBGR[0], e->d_rectBGR[1], e->d_rectGray[0], e->d_rectGray[1], e->rectW, e->rectH,
+	                                        initLeftDisparity, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
 	const int k = tsgmCheckSize(e, e->rectW, e->rectH, minResolution);
 	if (k == 0) return SGMHIP_E_ARG;
-	SGMCHK(e, hipSetDevice(e->device));
 	return tsgmRun(e, e->d_rectBGR[0], e->d_rectBGR[1], e->d_rectGray[0], e->d_rectGray[1], e->d_rectMask[0], e->d_rectMask[1], e->rectW, e->rectH, k,
 	               initLeftDisparity, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
 }

@@ -22,6 +22,8 @@ class SGMHipStats(C.Structure):
 _TYPES = {"SGMHipPixelData": PIXEL_DTYPE, "SGMHipStats": SGMHipStats}          # the mirrors by their names in include/sgmhip.h
 _SIGNATURES = _cabi.signatures("sgmhip.h", _TYPES)
 EXPORTS = list(_SIGNATURES)          # every function include/sgmhip.h declares
+_PLAIN_SIGNATURES = _cabi.signatures("sgmhip_plain.h", _TYPES)          # ... and its companion header, which sgmhip.h includes
+PLAIN_EXPORTS = list(_PLAIN_SIGNATURES)
 _LIB = None
 
 
@@ -35,7 +37,7 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "hipemu_counters") and os.environ.get("OPENMVS_AMD_TEST_EMULATOR") != "1":
             # tests/cpp/hipemu builds of the kernels exist for the CPU test-suite only; the product never computes on the host
             raise RuntimeError("%s is a CPU-emulated test build, not a device library: refusing to load it outside the test-suite" % path)
-        _LIB = _cabi.declare(lib, _SIGNATURES)
+        _LIB = _cabi.declare(_cabi.declare(lib, _SIGNATURES), _PLAIN_SIGNATURES)
     return _LIB
 
 
@@ -58,6 +60,18 @@ def make_pixels(ranges_min: np.ndarray, ranges_max: np.ndarray):
 
 class SGMError(RuntimeError):
     pass
+
+
+MAX_UNIFORM_DISP = 1024      # SGMHIP_MAX_UNIFORM_DISP
+
+
+def plain_range(seed):
+    """sgmhip_plain_range: the global range of plain SGM from the seed disparity map (host code of the library; no engine needed)."""
+    a = np.ascontiguousarray(seed, np.int16)
+    mn = C.c_int16(0); mx = C.c_int16(0)
+    if load_library().sgmhip_plain_range(a, a.size, C.byref(mn), C.byref(mx)) != 0:
+        raise SGMError("plain_range: the seed map is empty")
+    return int(mn.value), int(mx.value)
 
 
 class SemiGlobalMatcherHIP:
@@ -83,6 +97,19 @@ class SemiGlobalMatcherHIP:
         assert px.dtype == PIXEL_DTYPE and px.size == (w - 6) * (h - 6)
         self._shape = (h - 6, w - 6); self._num = num_costs
         self._chk(self._lib.sgmhip_set_problem(self._h, lb, lg, rg, w, h, px, num_costs, max_num_disp))
+
+    def set_problem_uniform(self, left_bgr, left_gray, right_gray, min_disp, max_disp):
+        """The problem of one range [min_disp, max_disp) for every pixel, idx = pixel * D, D <= MAX_UNIFORM_DISP: no pixel table travels
+        (sgmhip_set_problem_uniform); Match, results, set_disparity and RefineDisparityMap work on it as on any other."""
+        lb = np.ascontiguousarray(left_bgr, np.uint8); lg = np.ascontiguousarray(left_gray, np.float32); rg = np.ascontiguousarray(right_gray, np.float32)
+        h, w = lg.shape
+        assert lb.shape == (h, w, 3) and rg.shape == (h, w)
+        self._chk(self._lib.sgmhip_set_problem_uniform(self._h, lb, lg, rg, w, h, int(min_disp), int(max_disp)))
+        self._shape = (h - 6, w - 6); self._num = (h - 6) * (w - 6) * (int(max_disp) - int(min_disp))
+
+    def plain_range(self, seed):
+        """-> (minDisp, maxDisp) of plain SGM from the half-resolution seed map (sgmhip_plain_range: the reference's int16 arithmetic, wraps included)."""
+        return plain_range(seed)
 
     def set_sub_group_kernels(self, lanes):
         """Match with sub-groups of `lanes` (8, 16, 32; True = 16) lanes per pixel / pair / line (narrow tSGM ranges) instead of one wavefront each

@@ -52,6 +52,65 @@ def resize_nearest_u8(img: np.ndarray, w: int, h: int) -> np.ndarray:
     return img[ys][:, xs]
 
 
+MAX_UNIFORM_DISP = 1024      # SGMHIP_MAX_UNIFORM_DISP (include/sgmhip.h)
+
+
+def plain_range(seed) -> tuple:
+    """The global disparity range of plain SGM (:644-661; the numpy twin of sgmhip_plain_range): min and max over the seed, NO_DISP entries included, then
+    numDisp = (max - min) + 16, disp = min + max, [disp - numDisp, disp + numDisp) -- every intermediate a Disparity (int16) that wraps as one."""
+    a = np.asarray(seed, np.int16)
+    if a.size == 0:
+        raise ValueError("plain_range: the seed map is empty")
+    i16 = lambda v: int(np.array(v, np.int64).astype(np.int16))
+    mn, mx = int(a.min()), int(a.max())
+    num = i16(i16(mx - mn) + 16)
+    disp = i16(mn + mx)
+    return i16(disp - num), i16(disp + num)
+
+
+def _plain_match(be, left_bgr, left_gray, right_bgr, right_gray, init_left_disparity, n_speckle_size, subpixel_mode, subpixel_steps):
+    """Plain SGM (minResolution = 0, :585-590, 643-706): one level at full resolution, every pixel with the global range of the half-resolution seed.  Match(right,
+    left) takes that range as it is, Match(left, right) its negation -- the reference's assignment, the opposite of the tSGM branch.  The reference also crops the
+    masks and extracts them again after the filtering (:612-617, 705-706) and never reads them: they are not computed here."""
+    h, w = left_gray.shape
+    sh = (int(np.rint(h * 0.5)) - 2 * HW, int(np.rint(w * 0.5)) - 2 * HW)                  # Image8U::computeResize(size, 0.5), :611-625
+    if h <= 2 * HW or w <= 2 * HW or sh[0] <= 0 or sh[1] <= 0:
+        raise ValueError("plain SGM: the half-resolution seed grid of a %d x %d image is empty" % (w, h))
+    if init_left_disparity is not None:
+        seed = np.ascontiguousarray(init_left_disparity, np.int16)
+        if seed.shape != sh:
+            raise ValueError("initial disparity map must be %dx%d" % (sh[1], sh[0]))
+    else:
+        seed = np.full(sh, NO_DISP, np.int16)
+    mn, mx = plain_range(seed)
+    D = mx - mn
+    if D <= 0 or D > MAX_UNIFORM_DISP or mn < -32767:
+        raise ValueError("plain SGM: the seed's disparities span %d .. %d (min, max), which gives the range [%d, %d), D = %d: it must hold 1 .. %d disparities"
+                         % (int(seed.min()), int(seed.max()), mn, mx, D, MAX_UNIFORM_DISP))
+
+    def match(bgr, ga, gb, a, b):
+        if hasattr(be, "set_problem_uniform"):
+            be.set_problem_uniform(bgr, ga, gb, a, b)
+        else:
+            n = (h - 2 * HW) * (w - 2 * HW)
+            px = np.zeros(n, [("idx", np.uint64), ("minDisp", np.int16), ("maxDisp", np.int16), ("pad_", np.int32)])     # SGMHipPixelData
+            px["idx"] = np.arange(n, dtype=np.uint64) * np.uint64(b - a); px["minDisp"] = a; px["maxDisp"] = b
+            be.set_problem(bgr, ga, gb, px, n * (b - a), b - a)
+        be.Match()
+        return be.results()
+
+    right_disp, _ = match(right_bgr, right_gray, left_gray, mn, mx)                           # :667-676
+    left_disp, _ = match(left_bgr, left_gray, right_gray, -mx, -mn)                           # :678-685
+    left_disp = be.ConsistencyCrossCheck(left_disp, right_disp)                                # :698-706
+    right_disp = be.ConsistencyCrossCheck(right_disp, left_disp)
+    left_disp = be.FilterSpeckles(left_disp, n_speckle_size, 5)
+    right_disp = be.FilterSpeckles(right_disp, n_speckle_size, 5)
+    be.set_disparity(left_disp)
+    be.RefineDisparityMap(subpixel_mode, subpixel_steps)
+    refined, cost = be.results()
+    return refined, cost, 1
+
+
 def tsgm_match(be, left_bgr, left_gray, right_bgr, right_gray, left_mask, right_mask, min_resolution=320, init_left_disparity=None,
                n_speckle_size=100, subpixel_mode=6, subpixel_steps=4):
     """Runs the loop; returns (left disparity map at full resolution, refined to `subpixel_steps`, its cost map, the number of levels).
@@ -61,7 +120,7 @@ def tsgm_match(be, left_bgr, left_gray, right_bgr, right_gray, left_mask, right_
     H, W = left_gray.shape
     k = compute_scale(W, H, min_resolution)
     if k == 0:
-        raise NotImplementedError("plain SGM (minResolution = 0) needs the global range of an initial disparity map; only tSGM is driven here")
+        return _plain_match(be, left_bgr, left_gray, right_bgr, right_gray, init_left_disparity, n_speckle_size, subpixel_mode, subpixel_steps)
     left_disp = right_disp = None
     cost = None
     levels = 0
