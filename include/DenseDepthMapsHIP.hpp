@@ -13,6 +13,8 @@
 //   :411-414    a .dmap stored without normals: EstimateNormalMap from its depths         -> SetDepthMap(); EstimateMissingNormals()
 //   Mesh::Project (Mesh.cpp:3874-3968) of --mesh-file / --export-depth-maps-name          -> SetMesh(); ProjectMesh(); ReleaseMesh()
 //   DepthData::Save (DepthMap.cpp:234-252)                                                -> SaveDepthMaps() through include/dmapio.h
+//   :2099-2110, :2201-2206  the images and clouds of verbosity 3 and above                -> DepthImage(); ConfImage(); NormalImage(); ViewCloud()
+//   PointCloud::Save / SaveNViews / SaveWithScale (PointCloud.cpp:361-539)                 -> SavePointCloud()
 //
 // Needs nothing of OpenMVS / OpenCV: views are described by plain pointers (an OpenMVS caller fills them from MVS::Image / DepthData,
 // libs/MVS/DepthMap.h:157-271).  Throws std::runtime_error with the engine's message on any error, like PatchMatchHIP.hpp.
@@ -20,9 +22,11 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cfloat>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 #include "pmhip.h"
 
@@ -276,6 +280,83 @@ public:
 	}
 	void ReleaseMesh() { check(pmhip_mesh_release(e_)); }
 
+	// ---- the reference's image and PLY outputs, made on the device from the resident maps (include/pmhip_export.h).  The images come back as bytes for the host's own
+	// codec (ViewWidth x ViewHeight pixels, red first); PLY files are plain bytes and are written here, binary little endian with the header of PLY::header_complete.
+	// DepthMap2Image (ExportDepthMap): rgb gets 3 bytes per pixel; the range of the X84 rule unless minDepth / maxDepth are given; returns the range in use
+	std::pair<float, float> DepthImage(int idx, std::vector<unsigned char>& rgb, float minDepth = FLT_MAX, float maxDepth = 0) {
+		rgb.assign((size_t)ViewWidth(idx) * ViewHeight(idx) * 3, (unsigned char)0);
+		float range[2] = {0, 0};
+		check(pmhip_scene_depth_image(e_, idx, minDepth, maxDepth, rgb.data(), range));
+		return std::make_pair(range[0], range[1]);
+	}
+	// ExportNormalMap's image
+	void NormalImage(int idx, std::vector<unsigned char>& rgb) {
+		rgb.assign((size_t)ViewWidth(idx) * ViewHeight(idx) * 3, (unsigned char)0);
+		check(pmhip_scene_normal_image(e_, idx, rgb.data()));
+	}
+	// ExportConfidenceMap's image, one byte per pixel; false (and nothing to write) when no confidence is positive, as the reference returns
+	bool ConfImage(int idx, std::vector<unsigned char>& gray) {
+		gray.assign((size_t)ViewWidth(idx) * ViewHeight(idx), (unsigned char)0);
+		int empty = 0;
+		check(pmhip_scene_conf_image(e_, idx, gray.data(), nullptr, &empty));
+		return !empty;
+	}
+	// MVS::ExportPointCloud (DepthMap.cpp:1753-1870) of view idx into `path`, with normals (x y z nx ny nz red green blue) or without (x y z red green blue); false and
+	// no file when no depth is valid.  Returns through `count` the number of vertices.
+	bool ViewCloud(int idx, const std::string& path, bool withNormals = true, uint64_t* count = nullptr) {
+		uint64_t n = 0;
+		if (pmhip_scene_view_cloud(e_, idx, withNormals ? 1 : 0, nullptr, 0, &n) != PMHIP_OK && n == 0) check(PMHIP_E_ARG);   // (too small a capacity is how the count is asked for)
+		if (count) *count = n;
+		if (!n) return false;
+		std::vector<unsigned char> rec((size_t)n * (withNormals ? 27 : 15));
+		check(pmhip_scene_view_cloud(e_, idx, withNormals ? 1 : 0, rec.data(), n, &n));
+		std::string head = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) + "\nproperty float32 x\nproperty float32 y\nproperty float32 z\n";
+		if (withNormals) head += "property float32 nx\nproperty float32 ny\nproperty float32 nz\n";
+		head += "property uint8 red\nproperty uint8 green\nproperty uint8 blue\nend_header\n";
+		writeFile(path, head, rec.data(), rec.size());
+		return true;
+	}
+	// PointCloud::Save(path, bViews) of `pc` -- x y z [red green blue] [nx ny nz] [view_indices] [view_weights], properties in InitSaveProps' order (PointCloud.cpp:265-304);
+	// minViews > 0: PointCloud::SaveNViews (the points with at least that many views, white without colours); scaleMult > 0: PointCloud::SaveWithScale, the per-point
+	// scales computed on the device for the resident cloud (pmhip_scene_cloud_scale), which must be `pc` (as FuseDepthMaps / FinishPointCloud / FilterPointCloud left it).
+	// False and no file for an empty cloud.
+	bool SavePointCloud(const std::string& path, const PointCloud& pc, bool bViews = true, unsigned minViews = 0, float scaleMult = 0) {
+		const size_t n = pc.size();
+		if (!n) return false;
+		const bool color = !pc.colors.empty() || (minViews > 0 && scaleMult <= 0), normal = !pc.normals.empty(), lists = bViews && minViews == 0 && scaleMult <= 0 && !pc.views.empty();
+		const bool weights = lists && pc.weights.size() == pc.views.size();
+		std::vector<float> scale, conf;
+		if (scaleMult > 0) { scale.assign(n, 0.f); conf.assign(n, 0.f); check(pmhip_scene_cloud_scale(e_, scaleMult, scale.data(), conf.data())); }
+		std::vector<unsigned char> body;
+		auto put = [&body](const void* p, size_t bytes) { body.insert(body.end(), (const unsigned char*)p, (const unsigned char*)p + bytes); };
+		size_t kept = 0;
+		for (size_t i = 0; i < n; ++i) {
+			const uint32_t a = pc.viewStart[i], b = pc.viewStart[i + 1];
+			if (scaleMult <= 0 && minViews > 0 && b - a < minViews) continue;
+			++kept;
+			put(&pc.points[3 * i], 12);
+			if (color) { const unsigned char white[3] = {255, 255, 255}; const unsigned char* c = pc.colors.empty() ? white : &pc.colors[3 * i]; const unsigned char rgb[3] = {c[2], c[1], c[0]}; put(rgb, 3); }
+			if (normal) put(&pc.normals[3 * i], 12);
+			if (lists) {
+				if (b - a > 255) throw std::runtime_error("DenseDepthMapsHIP: a point with more than 255 views");
+				const unsigned char cnt = (unsigned char)(b - a);
+				put(&cnt, 1); put(&pc.views[a], 4 * (size_t)cnt);
+				if (weights) { put(&cnt, 1); put(&pc.weights[a], 4 * (size_t)cnt); }
+			}
+			if (scaleMult > 0) { put(&conf[i], 4); put(&scale[i], 4); }
+		}
+		if (!kept) return false;
+		std::string head = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(kept) + "\nproperty float32 x\nproperty float32 y\nproperty float32 z\n";
+		if (color) head += "property uint8 red\nproperty uint8 green\nproperty uint8 blue\n";
+		if (normal) head += "property float32 nx\nproperty float32 ny\nproperty float32 nz\n";
+		if (lists) head += "property list uint8 uint32 view_indices\n";
+		if (weights) head += "property list uint8 float32 view_weights\n";
+		if (scaleMult > 0) head += "property float32 confidence\nproperty float32 value\n";
+		head += "end_header\n";
+		writeFile(path, head, body.data(), body.size());
+		return true;
+	}
+
 	// One view's maps back to the host (any pointer may be null); ViewWidth(idx) x ViewHeight(idx) entries
 	void GetMaps(int idx, float* depth, float* normal, float* conf) { check(pmhip_scene_get_maps(e_, idx, depth, normal, conf)); }
 	int ViewWidth(int idx) const { return views_[(size_t)idx].w > 0 ? views_[(size_t)idx].w : w_; }
@@ -307,6 +388,12 @@ public:
 	pmhip_engine* engine() { return e_; }
 
 private:
+	static void writeFile(const std::string& path, const std::string& head, const unsigned char* body, size_t bytes) {
+		FILE* f = std::fopen(path.c_str(), "wb");
+		const bool ok = f && std::fwrite(head.data(), 1, head.size(), f) == head.size() && std::fwrite(body, 1, bytes, f) == bytes;
+		if (f && std::fclose(f) != 0) throw std::runtime_error("DenseDepthMapsHIP: cannot write " + path);
+		if (!ok) throw std::runtime_error("DenseDepthMapsHIP: cannot write " + path);
+	}
 	void check(int rc) const {
 		if (rc != PMHIP_OK) throw std::runtime_error(std::string("pmhip: ") + (e_ ? pmhip_last_error(e_) : "no device"));
 	}

@@ -376,4 +376,5 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #endif
 #include "pmhip_normals.h"
 #include "pmhip_mesh.h"
+#include "pmhip_export.h"
 #endif /* PMHIP_H_ */

@@ -15,6 +15,7 @@
 #include "pm_image.hip"
 #include "pm_normal.hip"
 #include "pm_mesh.hip"
+#include "pm_export.hip"
 #include "hip_buf.h"
 #include <limits.h>
 #include <math.h>
@@ -147,6 +148,7 @@ struct Fuse : FuseWork {
 	DevBuf<uint8_t> bgr; CloudBufs out;
 	std::vector<unsigned char> hasBgr;
 	uint64_t nPoints = 0, nViews = 0, nDepths = 0, rounds = 0; bool haveColor = false, haveNormal = false;
+	bool haveWeight = false;   // the cloud carries view weights (PointCloud::pointWeights not empty): fused with nMinViewsFuse >= 2, or set / loaded with weights
 };
 // the finishing steps on the fused cloud (pm_cloud.hip): grow-only working buffers, freed with the scene
 struct Cloud {
@@ -223,10 +225,22 @@ struct MeshMem {
 	hipEvent_t ev[2] = {nullptr, nullptr};                   // bracket the clears and kernels of a batch (pmhip_mesh_get_stats)
 };
 
+// The image and PLY outputs (pm_host_export.hip): grow-only working buffers, independent of the scene like the image store, and the statistics of the last call
+struct ExportMem {
+	DevBuf<uint32_t> st;                                     // the selection's state and histogram (PMEX_WORDS)
+	DevBuf<float> stage;                                     // values / a depth map from the host
+	DevBuf<uint8_t> image, flags, records;                   // the image being made (whole words of four pixels); valid flags and packed records of a view's cloud
+	DevBuf<uint2> tileSums, tileOff; DevBuf<uint32_t> totals;
+	DevBuf<PMFuseCam> cams; DevBuf<float> scale;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	uint64_t launches = 0, us = 0;
+};
+
 struct pmhip_engine : SceneMem {
 	int device = 0;
 	ImageStore img;
 	MeshMem mesh;
+	ExportMem ex;
 	hipEvent_t imgEv[2] = {nullptr, nullptr};     // bracket every kernel of the store (PMHipImageStats::kernelMs)
 	hipStream_t stream = nullptr;
 	// view groups of a batch sweep on their own streams so that the tail of one group's diagonal launch
@@ -288,6 +302,13 @@ static void freeMesh(pmhip_engine* e) {
 	e->mesh.boxMax = box; e->mesh.batchBytes = bytes;
 }
 
+// ... and the working buffers of the image and PLY outputs
+static void freeExport(pmhip_engine* e) {
+	hipSetDevice(e->device);
+	for (hipEvent_t ev : e->ex.ev) if (ev) hipEventDestroy(ev);
+	e->ex = ExportMem{};
+}
+
 #include "pm_host_estimate.hip"
 
 static int collectStats(pmhip_engine* e) {
@@ -340,6 +361,7 @@ void pmhip_destroy(pmhip_engine* e) {
 	freeScene(e);
 	freeImages(e);
 	freeMesh(e);
+	freeExport(e);
 	for (hipEvent_t ev : e->imgEv) if (ev) hipEventDestroy(ev);
 	for (int g = 0; g < 16; ++g) { if (e->gstream[g]) hipStreamDestroy(e->gstream[g]); if (e->joinEv[g]) hipEventDestroy(e->joinEv[g]); }
 	if (e->forkEv) hipEventDestroy(e->forkEv);
@@ -360,6 +382,7 @@ int pmhip_release(pmhip_engine* e) {
 	freeScene(e);
 	freeImages(e);
 	freeMesh(e);
+	freeExport(e);
 	e->inited = false;
 	return 0;
 }
@@ -879,3 +902,4 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #include "pm_host_image.hip"
 #include "pm_host_normal.hip"
 #include "pm_host_mesh.hip"
+#include "pm_host_export.hip"

@@ -213,7 +213,7 @@ static int loadCloud(pmhip_engine* e, const std::string& who, const char* what, 
 		HIPCHK(e, hipMemsetAsync(f.out.projs, 0, sizeof(uint16_t) * 2 * nV, e->stream));
 	}
 	HIPCHK(e, hipStreamSynchronize(e->stream));
-	f.nPoints = nPoints; f.nViews = nV; f.nDepths = 0; f.rounds = 0; f.haveColor = colors != nullptr; f.haveNormal = normals != nullptr;
+	f.nPoints = nPoints; f.nViews = nV; f.nDepths = 0; f.rounds = 0; f.haveColor = colors != nullptr; f.haveNormal = normals != nullptr; f.haveWeight = weights != nullptr;
 	return 0;
 }
 

@@ -160,7 +160,7 @@ int pmhip_scene_fuse(pmhip_engine* e, const int32_t* order, int nOrder, const PM
 	HIPCHK(e, hipMemcpyAsync(f.pin, f.counters + 2, sizeof(uint32_t) * 2, hipMemcpyDeviceToHost, e->stream));
 	HIPCHK(e, hipMemcpyAsync(&nd, f.nDepthsDev, sizeof(nd), hipMemcpyDeviceToHost, e->stream));
 	HIPCHK(e, hipStreamSynchronize(e->stream));
-	f.nPoints = f.pin[0]; f.nViews = f.pin[1]; f.nDepths = nd; f.haveColor = wantColor; f.haveNormal = wantNormal;
+	f.nPoints = f.pin[0]; f.nViews = f.pin[1]; f.nDepths = nd; f.haveColor = wantColor; f.haveNormal = wantNormal; f.haveWeight = prm->nMinViewsFuse >= 2;   // (MergeDepthMaps leaves pointWeights empty)
 	const uint32_t last = (uint32_t)f.nViews;
 	HIPCHK(e, hipMemcpyAsync(f.out.viewStart + f.nPoints, &last, sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
 	HIPCHK(e, hipStreamSynchronize(e->stream));

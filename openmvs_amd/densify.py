@@ -11,11 +11,13 @@ import numpy as np
 from . import dmap as _dmap
 
 REMOVE_SPECKLES, FILL_GAPS, ADJUST_FILTER = 1, 2, 4   # OPTDENSE::DepthFlags, libs/MVS/DepthMap.h:87-92
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")   # what `--export-depth-maps-name` may name besides .dmap and .pfm: the image writer fails on anything else
 
 
 def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_adjust: bool = True,
                        n_speckle_size: int = 100, n_ipol_gap_size: int = 7, f_depth_diff_threshold: float = 0.01,
-                       n_min_views_filter: int = 2, n_min_views_filter_adjust: int = 1, init_depth=None, init_normal=None, scene=None, dmap_dir=None, image_names=None):
+                       n_min_views_filter: int = 2, n_min_views_filter_adjust: int = 1, init_depth=None, init_normal=None, scene=None, dmap_dir=None, image_names=None,
+                       export=None):
     """Runs the reference's dense schedule for `view_ids` on a loaded scene (engine.scene_load / scene_set_view).
     `init_depth` / `init_normal` (dicts view id -> map) seed the photometric pass like `InitViews(..., loadDepthMaps=0)` does
     (SceneDensify.cpp:418-460); views without an entry start from random planes.
@@ -25,7 +27,10 @@ def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_a
     `dmap_dir` (needs `scene`): the reference's file-based checkpoint contract (SceneDensify.cpp:2010-2029,1943-1950).  A view whose `depthNNNN.dmap` is already there
     is NOT estimated in the photometric pass: its depth, normal and confidence maps are read back and the schedule carries on from them (every view takes part in the geometric
     rounds again, as there); every map is written when it has been estimated -- after the photometric pass, after each geometric round (the reference's .geo.dmap + rename)
-    and after the filters -- each file atomically (.tmp + rename, DepthData::Save).  Returns the views whose maps were resumed from files."""
+    and after the filters -- each file atomically (.tmp + rename, DepthData::Save).
+    `export`: called as export(stage, ids) where the reference writes its verbose per-view files: "raw" before the per-map filters (SceneDensify.cpp:2075-2076), "" after
+    them (EVT_SAVEDEPTHMAP, :2099-2110; after every estimation, as there) and "filtered" after the cross-view filter (:2201-2206).  Returns the views whose maps were
+    resumed from files."""
     ids = list(view_ids)
     if dmap_dir is not None and scene is None:
         raise ValueError("dmap_dir needs the scene (cameras, neighbours and depth ranges go into the files)")
@@ -42,17 +47,22 @@ def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_a
                 engine.scene_set_view(v, None, scene.K[v], scene.R[v], scene.C[v], float(scene.dmin[v]), float(scene.dmax[v]), scene.neighbors[v])
 
     def post():
+        if export is not None:
+            export("raw", ids)
         if n_optimize & REMOVE_SPECKLES:
             engine.scene_remove_small_segments(ids, n_speckle_size, f_depth_diff_threshold)
         if n_optimize & FILL_GAPS:
             engine.scene_gap_interpolation(ids, n_ipol_gap_size, f_depth_diff_threshold)
 
     def save(which):
+        if export is not None and which:
+            export("filtered" if which is filtered else "", which)
         if dmap_dir is not None and which:
             save_depth_maps(engine, scene, which, dmap_dir, image_names)
 
     engine.Init(False)
     resumed = []
+    filtered = list(ids)                                       # (its own list object: how `save` knows the call after the cross-view filter)
     for v in ids:
         engine.scene_reset_view(v)
         done = os.path.join(dmap_dir, _dmap.depth_file_name(int(v))) if dmap_dir is not None else None
@@ -92,7 +102,7 @@ def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_a
     image_neighbours()
     if n_optimize & ADJUST_FILTER:
         engine.scene_filter(ids, b_filter_adjust, n_min_views_filter, n_min_views_filter_adjust, f_depth_diff_threshold, commit=True)
-        save(ids)
+        save(filtered)
     return resumed
 
 
@@ -109,6 +119,35 @@ def save_depth_maps(engine, scene, view_ids, out_dir: str, image_names=None):
         _dmap.save(p, name, ids, size, scene.K[v], scene.R[v], scene.C[v], float(scene.dmin[v]), float(scene.dmax[v]), d, n, c)
         paths.append(p)
     return paths
+
+
+def export_view_files(engine, scene, ids, out_dir: str, level: int = 3, tag: str = "", image_saver=None) -> list:
+    """What the reference writes per view at verbosity `level` (EVT_SAVEDEPTHMAP, SceneDensify.cpp:2099-2110), made on the engine from the resident maps and named by
+    ComposeDepthFilePath (DepthMap.h:72): at level > 2 `depth%04u.png` (DepthMap2Image), `.conf.png` (ExportConfidenceMap; not written without a positive confidence)
+    and `.ply` (ExportPointCloud with normals; not written without a valid depth), at level > 4 also `.normal.png` and `.conf.pfm`.  `tag`: "raw" writes only
+    `depth%04u.raw.png`, and only at level > 3 (:2075-2076); "filtered" only `.filtered.png` and `.filtered.ply` (:2201-2206).  `scene` names nothing here: the file
+    number is the view's index.  `image_saver(path, array)`: how an (h, w[, 3]) uint8 image becomes a file (default `mapexport.save_image`, PIL).  Returns the files."""
+    from . import mapexport, plyio
+    save = image_saver or mapexport.save_image
+    out = []
+    if level <= 2 or (tag == "raw" and level <= 3):
+        return out
+    os.makedirs(out_dir, exist_ok=True)
+    for v in ids:
+        base = os.path.join(out_dir, "depth%04u." % int(v) + (tag + "." if tag else ""))
+        save(base + "png", engine.scene_depth_image(v)[0]); out.append(base + "png")
+        if tag == "raw":
+            continue
+        if tag == "":
+            conf = engine.scene_conf_image(v)
+            if conf is not None:
+                save(base + "conf.png", conf[0]); out.append(base + "conf.png")
+        if plyio.save_view_cloud(base + "ply", engine.scene_view_cloud(v, True), True):
+            out.append(base + "ply")
+        if tag == "" and level > 4:
+            save(base + "normal.png", engine.scene_normal_image(v)); out.append(base + "normal.png")
+            mapexport.save_pfm(base + "conf.pfm", engine.scene_get_maps(v)[2]); out.append(base + "conf.pfm")
+    return out
 
 
 # ---- scene front end: *.mvs + images -> engine scene -----------------------------------------------------------------------------
@@ -449,20 +488,23 @@ def replace_cloud_by_mesh(sc, mesh, image_sizes, engine=None, max_resolution: in
     return sc
 
 
-def export_mesh_depth_maps(scene, mesh, base_name: str, engine=None) -> list:
+def export_mesh_depth_maps(scene, mesh, base_name: str, engine=None, image_saver=None) -> list:
     """`Scene::ExportMeshToDepthMaps(baseName)` (libs/MVS/Scene.cpp:680-736; `DensifyPointCloud --export-depth-maps-name` with `--mesh-file`): the mesh rendered into
     every valid image at the working resolution -- `scene` is a `SceneViews` (`load_scene`), whose sizes and cameras come from the option table as there -- and one file
     per image, named insertBeforeFileExt(base_name, "%04u" % ID).  `.dmap`: depth and normals (vertex normals as `Mesh::ComputeNormalVertices` makes them), IDs = the
     image then its neighbours (`Image::neighbors`, the whole scored list), dMin 0.001, dMax FLT_MAX, no confidence; `.pfm`: depth only, as `TImage::Save` writes it
-    (little-endian, rows bottom to top).  Any other extension raises ValueError: the reference's colour-mapped PNG is not written.
+    (little-endian, rows bottom to top).  An image extension (`IMAGE_EXTENSIONS`), with an engine: the colour-mapped image of `ExportDepthMap` (DepthMap2Image with the range of its
+    X84 rule), made by the engine (`depth_image`, pmhip_depth_image) and written by `image_saver(path, array)` (default `mapexport.save_image`, PIL).  The image is the engine's work:
+    without an engine an image extension raises ValueError like any other name, it is not made on the host instead.
     `mesh`: a PLY file name or (vertices, faces); `engine`: a `PatchMatchHIP` that renders every image in one call (the mesh is released afterwards), None: the host
     twin `views.project_mesh`.  Returns the file names."""
     import numpy as np
-    from . import dmap, meshio, views
+    from . import dmap, mapexport, meshio, views
     i = base_name.rfind(".")
     ext = base_name[i:].lower() if i >= 0 else ""
-    if ext not in (".dmap", ".pfm"):
-        raise ValueError("export_mesh_depth_maps: extension '%s' of %s (.dmap: depth and normals, .pfm: depth)" % (ext, base_name))
+    if ext not in (".dmap", ".pfm") + (IMAGE_EXTENSIONS if engine is not None else ()):
+        raise ValueError("export_mesh_depth_maps: extension '%s' of %s (.dmap: depth and normals, .pfm: depth; with an engine also %s: the colour-mapped depth)"
+                         % (ext, base_name, " ".join(IMAGE_EXTENSIONS)))
     V, F = meshio.load_ply(mesh) if isinstance(mesh, (str, os.PathLike)) else mesh
     want_n = ext == ".dmap"
     n_img = scene.n_views - len(getattr(scene, "alias_of", None) or {})
@@ -483,10 +525,10 @@ def export_mesh_depth_maps(scene, mesh, base_name: str, engine=None) -> list:
         if want_n:
             nbs = scene.all_view_scores[v]["ID"] if v in (getattr(scene, "all_view_scores", None) or {}) else scene.neighbors[v]
             dmap.save(name, scene.names[v], [v] + [int(k) for k in nbs], scene.sizes[v], scene.K[v], scene.R[v], scene.C[v], 0.001, float(np.finfo(np.float32).max), depth, normal)
+        elif ext == ".pfm":
+            mapexport.save_pfm(name, depth)
         else:
-            with open(name, "wb") as f:
-                f.write(("Pf\n%d %d\n%f\n" % (depth.shape[1], depth.shape[0], -1.0)).encode("ascii"))
-                f.write(np.ascontiguousarray(depth[::-1], "<f4").tobytes())
+            (image_saver or mapexport.save_image)(name, engine.depth_image(depth)[0])
         out.append(name)
     return out
 
@@ -610,7 +652,8 @@ def filter_point_cloud(engine, mvs_in: str, mvs_out: str | None = None, th_remov
 
 def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None,
                          crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, prepare_on_device: bool = False, mesh_file: str | None = None,
-                         **load_args):
+                         export_level: int = 0, export_dir: str | None = None, ply_out: str | None = None, image_saver=None, export_number_views: int = 0,
+                         estimate_scale: float = 0.0, **load_args):
     """`Scene::DenseReconstruction(nFusionMode)` (libs/MVS/SceneDensify.cpp:1655-1750) for the PatchMatch path on one engine: prepare the views (`load_scene`), estimate all
     depth maps with the geometric rounds and the filters the option table asks for (`compute_depth_maps`; with `dmap_dir` under the reference's file contract), and -- unless
     `fusion_mode` is 1, "export depth maps only" -- fuse them and write `<scene>_dense.mvs` to `mvs_out`.  `opt`: an `optdense.OptDense` (default: the table's defaults with the
@@ -621,21 +664,40 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     `prepare_on_device`: the decoded images are resized, converted and resampled on the engine (`load_scene(..., engine=engine)`) -- the same depth maps and cloud, but the
     returned `SceneViews` has no host images (`gray[i]` / `bgr[i]` are None), which is why it is off by default.
     `mesh_file` (`--mesh-file`): a scene whose images carry no neighbours takes its sparse cloud from this mesh, rendered and tested on the engine (`load_scene(mesh=...)`).
+    `export_level` (the application's `-v`): above 2 the reference's per-view images and clouds are written into `export_dir` (default: `dmap_dir`, else the directory of
+    `ply_out` or `mvs_out`) by `export_view_files` -- `depthNNNN.raw.png` before the per-map filters (above 3), the `depthNNNN.*` set after them, `depthNNNN.filtered.*`
+    after the cross-view filter -- through `image_saver`.  `ply_out`: the final cloud as `<ply_out>.ply` (`PointCloud::Save`, DensifyPointCloud.cpp:421-423; a name that
+    already ends in .ply is used as it is).
+    `export_number_views` > 0 or `estimate_scale` > 0: `mvs_in` is an existing dense archive, as in the application (DensifyPointCloud.cpp:367-404): nothing is
+    estimated, `export_archive_clouds` writes `<ply_out>_Nviews.ply` / `<ply_out>_scale.ply`, and the call returns (None, None).
     Returns (SceneViews, cloud or None)."""
     from . import optdense
     th_filter = int(filter_point_cloud)
     if fusion_mode not in (0, 1):
         raise ValueError("fusion_mode %d: the PatchMatch path is modes 0 (estimate + fuse) and 1 (depth maps only)" % fusion_mode)
+    if export_number_views > 0 or estimate_scale > 0:
+        base = ply_out or mvs_out or os.path.splitext(mvs_in)[0]
+        export_archive_clouds(engine, mvs_in, base[:-4] if base.lower().endswith((".ply", ".mvs")) else base, export_number_views, estimate_scale)
+        return None, None
     if opt is None:
         opt = optdense.defaults(); opt.nNumViews = 8; opt.nEstimateNormals = 2
     if mesh_file is not None:
         load_args = dict(load_args, mesh=mesh_file, mesh_engine=engine)
     sv = load_scene(mvs_in, opt=opt, engine=engine if prepare_on_device else None, **load_args)
     engine.scene_load(sv, n_levels=int(opt.nSubResolutionLevels))
+    export = None
+    if export_level > 2:
+        where = export_dir or dmap_dir or os.path.dirname(os.path.abspath(ply_out or mvs_out or "."))
+        for i in sv.ids:                                             # the per-view clouds take their colours from the resident colour images
+            if sv.bgr[i] is not None:
+                engine.scene_set_color(i, sv.bgr[i])
+
+        def export(stage, ids):
+            export_view_files(engine, sv, ids, where, export_level, stage, image_saver)
     compute_depth_maps(engine, sv.ids, opt.params(seed), n_optimize=int(opt.nOptimize), b_filter_adjust=bool(opt.bFilterAdjust), n_speckle_size=int(opt.nSpeckleSize),
                        n_ipol_gap_size=int(opt.nIpolGapSize), f_depth_diff_threshold=float(opt.fDepthDiffThreshold), n_min_views_filter=int(opt.nMinViewsFilter),
                        n_min_views_filter_adjust=int(opt.nMinViewsFilterAdjust), init_depth=sv.init_depth, init_normal=sv.init_normal, scene=sv, dmap_dir=dmap_dir,
-                       image_names=sv.names)
+                       image_names=sv.names, export=export)
     if fusion_mode == 1:
         return sv, None
     cloud = fuse_depth_maps(engine, sv, opt, bgr=sv.bgr)
@@ -648,4 +710,41 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
         cloud = dict(engine.scene_cloud_filter(th_remove=th_filter, cam_C=C, cam_angle=ang), **extra)
     if mvs_out:
         save_dense_scene(mvs_in, mvs_out, cloud, sv)
+    if ply_out:
+        from . import plyio
+        plyio.save_point_cloud(ply_out if ply_out.lower().endswith(".ply") else ply_out + ".ply", cloud)
     return sv, cloud
+
+
+def export_archive_clouds(engine, mvs_in: str, base_name: str, export_number_views: int = 0, estimate_scale: float = 0.0) -> list:
+    """The application's two PLY exports of an existing archive: `--export-number-views N` with N > 0 writes `<base>_Nviews.ply` (`PointCloud::SaveNViews`,
+    DensifyPointCloud.cpp:375-382), `--estimate-scale s` with s > 0 writes `<base>_scale.ply` (`PointCloud::SaveWithScale` with scaleMult = s, :390-402) -- an archive
+    without normals gets them first from `pmhip_scene_cloud_finish`'s PCA normals (EstimatePointNormals, as there).  The cloud is the archive's, the cameras are each
+    image's at its own resolution, and the per-point scales are computed on the engine (`scene_cloud_scale`), which gets a scene of cameras only.  Returns the files."""
+    import numpy as np
+    from . import mvsi, plyio
+    sc = mvsi.load(mvs_in)
+    P = len(sc.vertices)
+    cloud = dict(nPoints=P, points=sc.vertices, viewStart=np.asarray(sc.vertex_view_start, np.uint32), views=np.ascontiguousarray(sc.vertex_views["image_id"], np.uint32),
+                 weights=np.ascontiguousarray(sc.vertex_views["confidence"], np.float32), colors=sc.vertices_color if len(sc.vertices_color) == P and P else None,
+                 normals=sc.vertices_normal if len(sc.vertices_normal) == P and P else None)
+    out = []
+    if export_number_views > 0:
+        name = "%s_%dviews.ply" % (base_name, export_number_views)
+        if plyio.save_point_cloud(name, cloud, min_views=int(export_number_views)):
+            out.append(name)
+    if estimate_scale > 0 and P:
+        n = len(sc.images)
+        cams = [sc.camera(i) if sc.images[i].is_valid() else None for i in range(n)]
+        w, h = next((c[3], c[4]) for c in cams if c is not None)
+        engine.scene_create(max(n, 2), max(int(w), 9), max(int(h), 9), 0)
+        for i, c in enumerate(cams):
+            if c is not None:
+                engine.scene_set_view(i, None, c[0], c[1], c[2], 0.1, 100.0, [])
+        engine.scene_cloud_load(cloud["points"], cloud["viewStart"], cloud["views"], cloud["weights"], cloud["colors"], cloud["normals"])
+        if cloud["normals"] is None:
+            cloud = dict(cloud, normals=engine.scene_cloud_finish(estimate_normals=True)["normals"])
+        name = base_name + "_scale.ply"
+        if plyio.save_point_cloud(name, cloud, scales=engine.scene_cloud_scale(float(estimate_scale))):
+            out.append(name)
+    return out

@@ -79,6 +79,8 @@ _NORMALS_SIGNATURES = _cabi.signatures("pmhip_normals.h", _TYPES)          # ...
 NORMALS_EXPORTS = list(_NORMALS_SIGNATURES)
 _MESH_SIGNATURES = _cabi.signatures("pmhip_mesh.h", _TYPES)
 MESH_EXPORTS = list(_MESH_SIGNATURES)
+_EXPORT_SIGNATURES = _cabi.signatures("pmhip_export.h", _TYPES)
+EXPORT_EXPORTS = list(_EXPORT_SIGNATURES)
 
 _LIB = None
 
@@ -98,6 +100,7 @@ def load_library() -> C.CDLL:
         _cabi.declare(lib, _SIGNATURES, allow_missing=experiment)
         _cabi.declare(lib, _NORMALS_SIGNATURES, allow_missing=experiment)
         _cabi.declare(lib, _MESH_SIGNATURES, allow_missing=experiment)
+        _cabi.declare(lib, _EXPORT_SIGNATURES, allow_missing=experiment)
         if hasattr(lib, "pmhip_abi_version") and lib.pmhip_abi_version() != PMHIP_ABI_VERSION and not experiment:
             raise RuntimeError("%s has struct layout version %d, these bindings are written for %d (include/pmhip.h)" % (path, lib.pmhip_abi_version(), PMHIP_ABI_VERSION))
         _LIB = lib
@@ -467,6 +470,79 @@ class PatchMatchHIP:
         out = np.zeros(5, np.uint64)
         self._chk(self._lib.pmhip_mesh_get_stats(self._h, out))
         return dict(zip(("batches", "large_faces", "box_pixels", "batch_bytes", "device_us"), (int(v) for v in out)))
+
+    # -- the reference's image and PLY outputs from the resident scene (include/pmhip_export.h) ----
+    def x84_threshold(self, values, mul=5.2):
+        """`mapexport.x84_threshold` on the device (pmhip_x84_threshold): (median, mul * MAD, min, max) of the values > 0 as float32; raises without one."""
+        v = np.ascontiguousarray(values, np.float32).ravel()
+        out = np.zeros(4, np.float32)
+        self._chk(self._lib.pmhip_x84_threshold(self._h, v, v.size, float(mul), out))
+        return tuple(out)
+
+    @staticmethod
+    def _range(min_depth, max_depth):
+        auto = min_depth is None or max_depth is None
+        return (float(np.finfo(np.float32).max), 0.0) if auto else (float(min_depth), float(max_depth))
+
+    def scene_depth_image(self, idx, min_depth=None, max_depth=None):
+        """`mapexport.depth_map_to_image` of a view's resident depth map (pmhip_scene_depth_image) -> ((h, w, 3) uint8 red first, (minDepth, maxDepth) in use)."""
+        w, h = self.view_size(idx)
+        rgb = np.zeros((h, w, 3), np.uint8); rng = np.zeros(2, np.float32)
+        self._chk(self._lib.pmhip_scene_depth_image(self._h, idx, *self._range(min_depth, max_depth), rgb, rng))
+        return rgb, (rng[0], rng[1])
+
+    def depth_image(self, depth, min_depth=None, max_depth=None):
+        """The same of a depth map on the host, a rendered mesh for one (pmhip_depth_image); needs no scene."""
+        d = np.ascontiguousarray(depth, np.float32)
+        if d.ndim != 2:
+            raise ValueError("depth must be (h, w)")
+        rgb = np.zeros(d.shape + (3,), np.uint8); rng = np.zeros(2, np.float32)
+        self._chk(self._lib.pmhip_depth_image(self._h, d, d.shape[1], d.shape[0], *self._range(min_depth, max_depth), rgb, rng))
+        return rgb, (rng[0], rng[1])
+
+    def scene_normal_image(self, idx):
+        """`mapexport.normal_map_to_image` of a view's resident normal map (pmhip_scene_normal_image) -> (h, w, 3) uint8."""
+        w, h = self.view_size(idx)
+        rgb = np.zeros((h, w, 3), np.uint8)
+        self._chk(self._lib.pmhip_scene_normal_image(self._h, idx, rgb))
+        return rgb
+
+    def scene_conf_image(self, idx):
+        """`mapexport.conf_map_to_image` of a view's resident confidence map (pmhip_scene_conf_image) -> ((h, w) uint8, (minConf, maxConf)), or None when no
+        confidence is positive."""
+        w, h = self.view_size(idx)
+        gray = np.zeros((h, w), np.uint8); rng = np.zeros(2, np.float32); empty = C.c_int(0)
+        self._chk(self._lib.pmhip_scene_conf_image(self._h, idx, gray, rng, C.byref(empty)))
+        return None if empty.value else (gray, (rng[0], rng[1]))
+
+    def scene_view_cloud(self, idx, with_normals=True, capacity=None):
+        """`mapexport.view_point_cloud` of a view's resident maps and colour image (pmhip_scene_view_cloud): the records as `mapexport.VIEW_VERTEX_N` /
+        `VIEW_VERTEX`.  `capacity` None: asked for first (two calls); a capacity that is too small raises, as the library refuses it."""
+        from . import mapexport
+        dt = mapexport.VIEW_VERTEX_N if with_normals else mapexport.VIEW_VERTEX
+        cnt = C.c_uint64(0)
+        if capacity is None:
+            rc = self._lib.pmhip_scene_view_cloud(self._h, idx, bool(with_normals), None, 0, C.byref(cnt))
+            if rc != 0 and cnt.value == 0:
+                self._chk(rc)
+            capacity = cnt.value
+        rec = np.zeros(int(capacity), dt)
+        self._chk(self._lib.pmhip_scene_view_cloud(self._h, idx, bool(with_normals), rec if capacity else None, int(capacity), C.byref(cnt)))
+        return rec[:cnt.value]
+
+    def scene_cloud_scale(self, scale_mult=1.0):
+        """`mapexport.point_scales` of the resident cloud with the scene's cameras (pmhip_scene_cloud_scale) -> (scale, confidence), float32 per point."""
+        nP = C.c_uint64()
+        self._chk(self._lib.pmhip_scene_cloud_finish(self._h, C.byref(PMHipCloudParams()), C.byref(nP), None))
+        scale = np.zeros(int(nP.value), np.float32); conf = np.zeros(int(nP.value), np.float32)
+        self._chk(self._lib.pmhip_scene_cloud_scale(self._h, float(scale_mult), scale, conf))
+        return scale, conf
+
+    def export_stats(self):
+        """pmhip_export_get_stats -> {quantum, grid_cap, scan_tile (work quanta in force), launches, device_us (of the last export call: kernels and download, by HIP events)}."""
+        out = np.zeros(8, np.uint64)
+        self._chk(self._lib.pmhip_export_get_stats(self._h, out))
+        return dict(zip(("quantum", "grid_cap", "scan_tile", "launches", "device_us"), (int(v) for v in out)))
 
     def scene_set_color(self, idx, bgr):
         """8-bit BGR image of a view at depth-map resolution (only fusion with bEstimateColor reads it)."""
