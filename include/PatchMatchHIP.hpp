@@ -82,6 +82,15 @@ public:
 		                                      geom_ ? (nGeometricIter < 0 ? 0 : nGeometricIter) : -1));
 	}
 
+	// The engine behind the adapter, for the calls of pmhip.h the class does not wrap (a resident scene: pmhip_scene_create / _set_view / _estimate / _get_maps)
+	pmhip_engine* engine() const { return engine_; }
+	// The initial depth and normal map of scene view `view` rasterised on the device from the view's point mesh (mvsf_point_mesh, include/mvsfront_mesh.h) instead of
+	// being made on the host and uploaded (pmhip_scene_seed_view, include/pmhip_seed.h): mode PMHIP_SEED_POINTS (bInitSparse, the 2x2 splats) or PMHIP_SEED_FACES;
+	// proj 2 * nVerts pixel coordinates, z nVerts depths, normals 3 * nVerts or nullptr (the resident normal map stays), faces 3 * nFaces vertex indices.
+	void SeedView(int view, int mode, const float* proj, const float* z, const float* normals, uint32_t nVerts, const uint32_t* faces, uint32_t nFaces) {
+		check(pmhip_scene_seed_view(engine_, view, mode, proj, z, normals, nVerts, faces, nFaces));
+	}
+
 private:
 	static void copy9(const double* s, double* d) { for (int i = 0; i < 9; ++i) d[i] = s[i]; }
 	static void copy3(const double* s, double* d) { for (int i = 0; i < 3; ++i) d[i] = s[i]; }

@@ -88,4 +88,5 @@ int mvsf_estimate_normal_map(const double K[9], const float* depth, int w, int h
 #ifdef __cplusplus
 }
 #endif
+#include "mvsfront_mesh.h"
 #endif /* MVSFRONT_H_ */

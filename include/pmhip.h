@@ -377,4 +377,5 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #include "pmhip_normals.h"
 #include "pmhip_mesh.h"
 #include "pmhip_export.h"
+#include "pmhip_seed.h"
 #endif /* PMHIP_H_ */

@@ -165,4 +165,5 @@ int sgmhip_stats_get(sgmhip_engine* e, SGMHipStats* out);
 }
 #endif
 #include "sgmhip_plain.h"
+#include "sgmhip_seed.h"
 #endif /* SGMHIP_H_ */

@@ -18,8 +18,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-ffp
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-value", "-Wno-pass-failed"]
 
 LIBS = {
-    "libpmhip.so": (["pm_engine.hip"], ["pm_kernels.hip", "pm_band.hip", "pm_wide_n.hip", "pm_filter.hip", "pm_fuse.hip", "pm_fuse.h", "pm_cloud.hip", "pm_cloud_filter.hip", "pm_image.hip", "pm_normal.hip", "pm_mesh.hip", "pm_export.hip", "pm_host_estimate.hip", "pm_host_filter.hip", "pm_host_fuse.hip", "pm_host_cloud.hip", "pm_host_image.hip", "pm_host_normal.hip", "pm_host_mesh.hip", "pm_host_export.hip", "hip_buf.h", "pm_math.h", "../../include/pmhip.h", "../../include/pmhip_normals.h", "../../include/pmhip_mesh.h", "../../include/pmhip_export.h"]),
-    "libsgmhip.so": (["sgm_engine.hip"], ["sgm_kernels.hip", "sgm_kernels_sub.hip", "sgm_kernels_wide.hip", "sgm_tsgm.hip", "sgm_rectify.hip", "sgm_post.hip", "sgm_post.h", "hip_buf.h", "pm_math.h", "../../include/sgmhip.h", "../../include/sgmhip_plain.h"]),
+    "libpmhip.so": (["pm_engine.hip"], ["pm_kernels.hip", "pm_band.hip", "pm_wide_n.hip", "pm_filter.hip", "pm_fuse.hip", "pm_fuse.h", "pm_cloud.hip", "pm_cloud_filter.hip", "pm_image.hip", "pm_normal.hip", "pm_mesh.hip", "pm_export.hip", "seed_raster.hip", "pm_host_estimate.hip", "pm_host_filter.hip", "pm_host_fuse.hip", "pm_host_cloud.hip", "pm_host_image.hip", "pm_host_normal.hip", "pm_host_mesh.hip", "pm_host_export.hip", "pm_host_seed.hip", "hip_buf.h", "pm_math.h", "../../include/pmhip.h", "../../include/pmhip_normals.h", "../../include/pmhip_mesh.h", "../../include/pmhip_export.h", "../../include/pmhip_seed.h"]),
+    "libsgmhip.so": (["sgm_engine.hip"], ["sgm_kernels.hip", "sgm_kernels_sub.hip", "sgm_kernels_wide.hip", "sgm_tsgm.hip", "sgm_rectify.hip", "seed_raster.hip", "sgm_post.hip", "sgm_post.h", "hip_buf.h", "pm_math.h", "../../include/sgmhip.h", "../../include/sgmhip_plain.h", "../../include/sgmhip_seed.h"]),
 }
 
 
@@ -31,7 +31,7 @@ LIBS = {
 LIB_FLAGS = {"libsgmhip.so": ["-fno-slp-vectorize"], "libpmhip.so": ["-fno-slp-vectorize"]}
 
 HOST_LIBS = {"libdmapio.so": (["dmap_io.cpp"], ["../../include/dmapio.h"]),          # plain C++ (g++), no GPU code
-             "libmvsfront.so": (["mvs_front.cpp", "opt_dense.cpp"], ["sml_text.h", "../../include/mvsfront.h", "../../include/optdense.h", "../../include/pmhip.h"])}
+             "libmvsfront.so": (["mvs_front.cpp", "opt_dense.cpp"], ["sml_text.h", "../../include/mvsfront.h", "../../include/mvsfront_mesh.h", "../../include/optdense.h", "../../include/pmhip.h"])}
 
 
 def build_host_lib(name: str, force: bool = False) -> str | None:

@@ -16,6 +16,7 @@
 #include "pm_normal.hip"
 #include "pm_mesh.hip"
 #include "pm_export.hip"
+#include "seed_raster.hip"
 #include "hip_buf.h"
 #include <limits.h>
 #include <math.h>
@@ -241,6 +242,7 @@ struct pmhip_engine : SceneMem {
 	ImageStore img;
 	MeshMem mesh;
 	ExportMem ex;
+	SeedWork seed; DevBuf<float> seedDepth, seedNormal;   // the seed rasteriser (pm_host_seed.hip): its mesh and keys, and the maps of pmhip_seed_raster; independent of the scene
 	hipEvent_t imgEv[2] = {nullptr, nullptr};     // bracket every kernel of the store (PMHipImageStats::kernelMs)
 	hipStream_t stream = nullptr;
 	// view groups of a batch sweep on their own streams so that the tail of one group's diagonal launch
@@ -300,6 +302,12 @@ static void freeMesh(pmhip_engine* e) {
 	for (hipEvent_t ev : e->mesh.ev) if (ev) hipEventDestroy(ev);
 	e->mesh = MeshMem{};
 	e->mesh.boxMax = box; e->mesh.batchBytes = bytes;
+}
+
+// ... and the seed rasteriser's buffers (the tuning stays)
+static void freeSeed(pmhip_engine* e) {
+	hipSetDevice(e->device);
+	e->seed.free(); e->seedDepth.release(); e->seedNormal.release();
 }
 
 // ... and the working buffers of the image and PLY outputs
@@ -362,6 +370,7 @@ void pmhip_destroy(pmhip_engine* e) {
 	freeImages(e);
 	freeMesh(e);
 	freeExport(e);
+	freeSeed(e);
 	for (hipEvent_t ev : e->imgEv) if (ev) hipEventDestroy(ev);
 	for (int g = 0; g < 16; ++g) { if (e->gstream[g]) hipStreamDestroy(e->gstream[g]); if (e->joinEv[g]) hipEventDestroy(e->joinEv[g]); }
 	if (e->forkEv) hipEventDestroy(e->forkEv);
@@ -383,6 +392,7 @@ int pmhip_release(pmhip_engine* e) {
 	freeImages(e);
 	freeMesh(e);
 	freeExport(e);
+	freeSeed(e);
 	e->inited = false;
 	return 0;
 }
@@ -903,3 +913,4 @@ int pmhip_resample(pmhip_engine* e, int kind, const void* src, int sw, int sh, v
 #include "pm_host_normal.hip"
 #include "pm_host_mesh.hip"
 #include "pm_host_export.hip"
+#include "pm_host_seed.hip"

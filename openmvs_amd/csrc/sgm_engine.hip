@@ -6,6 +6,7 @@
 #include "sgm_post.hip"
 #include "sgm_tsgm.hip"
 #include "sgm_rectify.hip"
+#include "seed_raster.hip"
 #include "hip_buf.h"
 #include <math.h>
 #include <string.h>
@@ -36,7 +37,14 @@ struct sgmhip_engine : SGMProblemBufs {
 	struct SceneImage { DevBuf<unsigned char> bgr; int w = 0, h = 0; }; std::vector<SceneImage> scene;
 	DevBuf<unsigned char> d_rectBGR[2], d_rectMask[2]; DevBuf<float> d_rectGray[2], d_srgb; size_t capRect = 0; int rectW = 0, rectH = 0;
 	double rectMs = 0; uint64_t rectCalls = 0;     // HIP-event time of the rectification kernel since the last sgmhip_stats_reset
+	// the resident seed (include/sgmhip_seed.h): the rasteriser's mesh and keys, the depth map of the last sgmhip_seed_raster (seedW = 0: none) and the initial left
+	// disparity of the last sgmhip_seed_disparity (seedDispW = 0: none)
+	SeedWork seed; DevBuf<float> d_seedDepth; int seedW = 0, seedH = 0; DevBuf<int16_t> d_seedDisp; int seedDispW = 0, seedDispH = 0;
 };
+static void sgmFreeSeed(sgmhip_engine* e) {
+	hipSetDevice(e->device);
+	e->seed.free(); e->d_seedDepth.release(); e->d_seedDisp.release(); e->seedW = e->seedH = e->seedDispW = e->seedDispH = 0;
+}
 
 static void sgmFree(sgmhip_engine* e) {
 	hipSetDevice(e->device);
@@ -87,6 +95,7 @@ void sgmhip_destroy(sgmhip_engine* e) {
 	hipSetDevice(e->device); hipStreamSynchronize(e->stream);
 	for (auto& ev : e->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
 	sgmFree(e); e->d_P2s.release(); e->d_uniform.release(); e->d_deltas.release();
+	sgmFreeSeed(e);
 	e->scene.clear(); e->d_srgb.release(); for (int s = 0; s < 2; ++s) { e->d_rectBGR[s].release(); e->d_rectGray[s].release(); e->d_rectMask[s].release(); }
 	hipStreamDestroy(e->stream); delete e;
 }
@@ -634,7 +643,7 @@ static int tsgmCheckSize(sgmhip_engine* e, int w, int h, unsigned minResolution)
 // and sgmhip_tsgm_match_rectified runs on the outputs of sgmhip_rectify_pair
 static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned char* fRB, const float* fLG, const float* fRG, const unsigned char* fLM, const unsigned char* fRM,
 		int w, int h, int k, const int16_t* initLeftDisparity, int nSpeckleSize, int subpixelMode, int subpixelSteps, uint16_t P1, const uint16_t P2s[256],
-		int16_t* disparity, uint16_t* cost, int* numLevels) {
+		int16_t* disparity, uint16_t* cost, int* numLevels, bool initOnDevice = false) {
 	hipStream_t st = e->stream;
 	const size_t nFull = (size_t)w * h, nValid = (size_t)(w - 2 * SGM_HW) * (h - 2 * SGM_HW);
 	// the per-level working set (sized for the finest level)
@@ -697,7 +706,7 @@ static int tsgmRun(sgmhip_engine* e, const unsigned char* fLB, const unsigned ch
 			const int hw2 = cvRound(lw * 0.5), hh2 = cvRound(lh * 0.5);                 // Image8U::computeResize(size, 0.5), :622
 			dW = hw2 - 2 * SGM_HW; dH = hh2 - 2 * SGM_HW;
 			if (dW <= 0 || dH <= 0) { e->err = "tsgm: coarsest level too small"; return SGMHIP_E_ARG; }
-			if (initLeftDisparity) SGMCHK(e, hipMemcpyAsync(leftDisp, initLeftDisparity, (size_t)dW * dH * 2, hipMemcpyHostToDevice, st));
+			if (initLeftDisparity) SGMCHK(e, hipMemcpyAsync(leftDisp, initLeftDisparity, (size_t)dW * dH * 2, initOnDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
 			else hipLaunchKernelGGL(sgmt_fill_i16_kernel, dim3(gridFor((size_t)dW * dH)), dim3(256), 0, st, leftDisp, (size_t)dW * dH, (short)SGMP_NO_DISP);
 			hipLaunchKernelGGL(sgmt_mask_first_kernel, dim3(gridFor(nV)), dim3(256), 0, st, fLM, w, lm, vw, vh, f);   // :627-631
 			hipLaunchKernelGGL(sgmt_mask_first_kernel, dim3(gridFor(nV)), dim3(256), 0, st, fRM, w, rm, vw, vh, f);
@@ -835,6 +844,7 @@ int sgmhip_scene_clear(sgmhip_engine* e) {
 	SGMCHK(e, hipSetDevice(e->device));
 	SGMCHK(e, hipStreamSynchronize(e->stream));
 	e->scene.clear();
+	sgmFreeSeed(e);
 	return 0;
 }
 
@@ -900,6 +910,76 @@ int sgmhip_tsgm_match_rectified(sgmhip_engine* e, unsigned minResolution, const 
 	if (k == 0) return SGMHIP_E_ARG;
 	return tsgmRun(e, e->d_rectBGR[0], e->d_rectBGR[1], e->d_rectGray[0], e->d_rectGray[1], e->d_rectMask[0], e->d_rectMask[1], e->rectW, e->rectH, k,
 	               initLeftDisparity, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
+}
+
+// ---- the seed made and kept on the device (include/sgmhip_seed.h; kernels and launch sequence: seed_raster.hip) ------------------------------------------------
+int sgmhip_seed_raster(sgmhip_engine* e, int w, int h, const float* proj, const float* z, uint32_t nVerts, const uint32_t* faces, uint32_t nFaces, float* depthOut) {
+	if (!e) return SGMHIP_E_ARG;
+	const std::string why = seedCheck("seed_raster", SEED_MODE_FACES, w, h, proj, z, nVerts, faces, nFaces);
+	if (!why.empty()) { e->err = why; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	const size_t P = (size_t)w * h;
+	e->seedW = e->seedH = 0;
+	SGMCHK(e, e->d_seedDepth.reserve(P));
+	SGMCHK(e, seedRun(e->seed, e->stream, SEED_MODE_FACES, w, h, proj, z, nullptr, nVerts, faces, nFaces, e->d_seedDepth, nullptr));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	SGMCHK(e, seedCollect(e->seed, SEED_MODE_FACES, nVerts == 0 || nFaces == 0));
+	if (depthOut) SGMCHK(e, hipMemcpy(depthOut, e->d_seedDepth, sizeof(float) * P, hipMemcpyDeviceToHost));
+	e->seedW = w; e->seedH = h;
+	return 0;
+}
+
+int sgmhip_seed_disparity(sgmhip_engine* e, const double invH[9], const double invQ[16], int subpixelSteps, int w, int h, int16_t* disparityOut) {
+	if (!e) return SGMHIP_E_ARG;
+	if (!invH || !invQ || w <= 0 || h <= 0) { e->err = "seed_disparity: null matrix, or a width or height <= 0"; return SGMHIP_E_ARG; }
+	if (!e->seedW) { e->err = "no seed is resident: call sgmhip_seed_raster first"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	const size_t n = (size_t)w * h;
+	e->seedDispW = e->seedDispH = 0;
+	SGMCHK(e, e->d_seedDisp.reserve(n));
+	SGMPMat mh{}, mq{}; memcpy(mh.m, invH, 72); memcpy(mq.m, invQ, 128);
+	hipLaunchKernelGGL(sgmp_depth2disparity_kernel, dim3(gridFor(n)), dim3(256), 0, e->stream, (const float*)e->d_seedDepth.p, e->seedW, e->seedH, mh, mq, subpixelSteps,
+	                   e->d_seedDisp.p, w, h);
+	SGMCHK(e, hipGetLastError());
+	if (disparityOut) SGMCHK(e, hipMemcpyAsync(disparityOut, e->d_seedDisp, n * 2, hipMemcpyDeviceToHost, e->stream));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	e->seedDispW = w; e->seedDispH = h;
+	return 0;
+}
+
+int sgmhip_tsgm_match_rectified_seeded(sgmhip_engine* e, unsigned minResolution, int nSpeckleSize, int subpixelMode, int subpixelSteps,
+		uint16_t P1, const uint16_t P2s[256], int16_t* disparity, uint16_t* cost, int* numLevels) {
+	if (!e) return SGMHIP_E_ARG;
+	if (!P2s || !disparity || !cost || nSpeckleSize < 0 || subpixelMode < 0 || subpixelMode > SGMP_SUBPIXEL_LC_BLEND || subpixelSteps < 0 || subpixelSteps > 64) { e->err = "tsgm_match_rectified: null pointer or option out of range"; return SGMHIP_E_ARG; }
+	if (!e->rectW) { e->err = "no rectified pair is resident: call sgmhip_rectify_pair first"; return SGMHIP_E_ARG; }
+	if (!e->seedDispW) { e->err = "no seed disparity is resident: call sgmhip_seed_raster and sgmhip_seed_disparity first"; return SGMHIP_E_ARG; }
+	SGMCHK(e, hipSetDevice(e->device));
+	const int k = minResolution ? tsgmCheckSize(e, e->rectW, e->rectH, minResolution) : 0;
+	if (minResolution && k == 0) return SGMHIP_E_ARG;
+	// the first level's seed grid: Image8U::computeResize(level size, 0.5) less the window's border (tsgmRun, tsgmPlainRun)
+	const int dW = cvRound((e->rectW >> k) * 0.5) - 2 * SGM_HW, dH = cvRound((e->rectH >> k) * 0.5) - 2 * SGM_HW;
+	if (e->seedDispW != dW || e->seedDispH != dH) {
+		e->err = "tsgm_match_rectified_seeded: the resident seed disparity is " + std::to_string(e->seedDispW) + " x " + std::to_string(e->seedDispH) + ", the first level's seed grid " +
+		         std::to_string(dW) + " x " + std::to_string(dH);
+		return SGMHIP_E_ARG;
+	}
+	if (!minResolution) {   // the seed only gives the global range: its values come back for sgmhip_plain_range
+		std::vector<int16_t> host((size_t)dW * dH);
+		SGMCHK(e, hipMemcpyAsync(host.data(), e->d_seedDisp, host.size() * 2, hipMemcpyDeviceToHost, e->stream));
+		SGMCHK(e, hipStreamSynchronize(e->stream));
+		return tsgmPlainRun(e, e->d_rectBGR[0], e->d_rectBGR[1], e->d_rectGray[0], e->d_rectGray[1], e->rectW, e->rectH,
+		                    host.data(), nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels);
+	}
+	return tsgmRun(e, e->d_rectBGR[0], e->d_rectBGR[1], e->d_rectGray[0], e->d_rectGray[1], e->d_rectMask[0], e->d_rectMask[1], e->rectW, e->rectH, k,
+	               e->d_seedDisp, nSpeckleSize, subpixelMode, subpixelSteps, P1, P2s, disparity, cost, numLevels, true);
+}
+
+int sgmhip_seed_clear(sgmhip_engine* e) {
+	if (!e) return SGMHIP_E_ARG;
+	SGMCHK(e, hipSetDevice(e->device));
+	SGMCHK(e, hipStreamSynchronize(e->stream));
+	sgmFreeSeed(e);
+	return 0;
 }
 
 int sgmhip_rectify_stats_get(sgmhip_engine* e, double* kernelMs, uint64_t* calls) {

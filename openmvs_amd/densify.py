@@ -17,10 +17,12 @@ IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")   # what `
 def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_adjust: bool = True,
                        n_speckle_size: int = 100, n_ipol_gap_size: int = 7, f_depth_diff_threshold: float = 0.01,
                        n_min_views_filter: int = 2, n_min_views_filter_adjust: int = 1, init_depth=None, init_normal=None, scene=None, dmap_dir=None, image_names=None,
-                       export=None):
+                       export=None, seed_mesh=None):
     """Runs the reference's dense schedule for `view_ids` on a loaded scene (engine.scene_load / scene_set_view).
     `init_depth` / `init_normal` (dicts view id -> map) seed the photometric pass like `InitViews(..., loadDepthMaps=0)` does
     (SceneDensify.cpp:418-460); views without an entry start from random planes.
+    `seed_mesh` (dict view id -> (mode, proj, z, normals, faces), `SceneViews.seed_mesh`): the same maps rasterised on the device from the view's point mesh
+    (`engine.scene_seed_view`) where `scene_set_maps` would upload them; a view listed here does not read `init_depth`.
     `scene`: the `SceneViews` the engine was loaded from, needed when it holds resampled copies of neighbours (`alias_of`, ViewData::ScaleImage): at every round
     boundary a copy is handed the depth map of the image it stands for, at that image's size and camera (the neighbour's saved .dmap, SceneDensify.cpp:378-393), and
     before the cross-view filter the reference views get their image neighbours back (FilterDepthMap reads arrDepthData[ID], :1049-1299).
@@ -83,6 +85,9 @@ def compute_depth_maps(engine, view_ids, params, n_optimize: int = 7, b_filter_a
                 engine.scene_estimate_normals([v])
             engine.scene_set_conf(v, f["confidence_map"])
             resumed.append(v)
+        elif seed_mesh is not None and v in seed_mesh:
+            mode, proj, z, normals, faces = seed_mesh[v]
+            engine.scene_seed_view(v, mode, proj, z, normals, faces)
         elif init_depth is not None and v in init_depth:
             engine.scene_set_maps(v, init_depth[v], None if init_normal is None else init_normal.get(v))
     todo = [v for v in ids if v not in resumed]
@@ -162,6 +167,7 @@ class SceneViews:
         self.gray = []; self.K = []; self.R = []; self.C = []
         self.dmin = []; self.dmax = []; self.neighbors = []; self.view_scores = []
         self.init_depth = {}; self.init_normal = {}
+        self.seed_mesh = {}                         # load_scene(seed_on_device=True): image -> (mode, proj, z, normals, faces), the mesh `scene_seed_view` makes the init maps from
         self.names = []; self.ids = []          # ids: images that passed view selection, in scene order
         self.masks = {}; self.mask_option = False   # ignore masks by image index (1 = process, 0 = ignore); mask_option: OPTDENSE::nIgnoreMaskLabel >= 0
         self.sizes = []                             # (w, h) of every slot: images of another size than the scene's carry their own (pmhip_scene_set_view_sized)
@@ -348,7 +354,7 @@ def scale_image(gray, scale):
 
 
 def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=None, ignore_mask_label=None, mask_path=None, mask_loader=None, engine=None,
-               mesh=None, mesh_engine=None):
+               mesh=None, mesh_engine=None, seed_on_device=False):
     """Reads an MVSI scene and its images and runs view selection + depth initialisation for every valid image.
 
     `opt`: a `views.DenseOptions` or the whole option table (`optdense.OptDense`, e.g. from `optdense.load(<--dense-config-file>)`).
@@ -366,7 +372,10 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
     `mesh` (`DensifyPointCloud --mesh-file`: a PLY file name, or (vertices, faces)): when no image of the scene carries neighbours, the sparse cloud is replaced by the
     mesh's vertices with the images that see them (`views.sample_mesh_with_visibility`, Scene::ComputeDepthMaps, SceneDensify.cpp:1757-1760) before view selection;
     with `mesh_engine` (a `PatchMatchHIP`) the renders and the visibility test run on the device (`mesh_visibility`) and the mesh is released afterwards.  A scene with
-    neighbours ignores the mesh, as there.  Returns a `SceneViews`."""
+    neighbours ignores the mesh, as there.
+    `seed_on_device`: no `init_depth` / `init_normal` maps are made; `SceneViews.seed_mesh[i]` = (mode, proj, z, normals, faces) holds the point mesh
+    (`views.point_mesh`) from which `compute_depth_maps(..., seed_mesh=...)` has the engine rasterise the same maps (`scene_seed_view`).  The 5x5 splat of
+    `nMinViewsTrustPoint < 2` stays on the host route.  Returns a `SceneViews`."""
     import numpy as np
     from . import mvsi, views
     opt = opt or views.DenseOptions()
@@ -432,9 +441,14 @@ def load_scene(mvs_path: str, opt=None, image_loader=None, view_neighbors_file=N
             sv.neighbors.append(np.zeros(0, np.int32)); sv.view_scores.append(None); sv.dmin.append(0.1); sv.dmax.append(100.0)
             continue
         nb, points, sv.avg_depth[i] = sel
-        d, n, dmin, dmax = views.init_depth_map(sc, cams, i, points, opt)
         sv.ids.append(i); sv.neighbors.append(nb["ID"].astype(np.int32)); sv.view_scores.append(nb)
-        sv.dmin.append(dmin); sv.dmax.append(dmax); sv.init_depth[i] = d; sv.init_normal[i] = n
+        if seed_on_device and opt.nMinViewsTrustPoint >= 2:
+            proj, _, vz, normals, faces, dmin, dmax = views.point_mesh(sc, cams, i, points, opt)
+            sv.seed_mesh[i] = (1 if not opt.bInitSparse else 0, proj, vz, normals, faces)          # PMHIP_SEED_FACES / PMHIP_SEED_POINTS
+        else:
+            d, n, dmin, dmax = views.init_depth_map(sc, cams, i, points, opt)
+            sv.init_depth[i] = d; sv.init_normal[i] = n
+        sv.dmin.append(dmin); sv.dmax.append(dmax)
     # InitViews, SceneDensify.cpp:333-352: a neighbour whose footprint differs by 15 % or more enters the estimation as a RESAMPLED image with the camera of that size
     # (ViewData::ScaleImage).  Each (image, scale) pair becomes an extra source-only slot behind the images; the reference view's estimation list points at it, while
     # `neighbors` keeps the image itself -- whose own depth map, at its own size and camera, is what the geometric rounds, the cross-view filter and the fusion read
@@ -653,7 +667,7 @@ def filter_point_cloud(engine, mvs_in: str, mvs_out: str | None = None, th_remov
 def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=None, seed: int = 0, fusion_mode: int = 0, dmap_dir: str | None = None,
                          crop_to_roi: bool = False, border_roi: float = 0.0, filter_point_cloud: int = 0, prepare_on_device: bool = False, mesh_file: str | None = None,
                          export_level: int = 0, export_dir: str | None = None, ply_out: str | None = None, image_saver=None, export_number_views: int = 0,
-                         estimate_scale: float = 0.0, **load_args):
+                         estimate_scale: float = 0.0, seed_on_device: bool = False, **load_args):
     """`Scene::DenseReconstruction(nFusionMode)` (libs/MVS/SceneDensify.cpp:1655-1750) for the PatchMatch path on one engine: prepare the views (`load_scene`), estimate all
     depth maps with the geometric rounds and the filters the option table asks for (`compute_depth_maps`; with `dmap_dir` under the reference's file contract), and -- unless
     `fusion_mode` is 1, "export depth maps only" -- fuse them and write `<scene>_dense.mvs` to `mvs_out`.  `opt`: an `optdense.OptDense` (default: the table's defaults with the
@@ -663,6 +677,8 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     `filter_point_cloud` < 0: `Scene::PointCloudFilter` with that threshold on the finished cloud (`PatchMatchHIP.scene_cloud_filter`; default 0: off).
     `prepare_on_device`: the decoded images are resized, converted and resampled on the engine (`load_scene(..., engine=engine)`) -- the same depth maps and cloud, but the
     returned `SceneViews` has no host images (`gray[i]` / `bgr[i]` are None), which is why it is off by default.
+    `seed_on_device`: the initial depth and normal maps are rasterised on the engine from each view's point mesh (`load_scene(..., seed_on_device=True)`,
+    `scene_seed_view`) instead of being made on the host and uploaded -- the same bits; off by default, like `prepare_on_device`.
     `mesh_file` (`--mesh-file`): a scene whose images carry no neighbours takes its sparse cloud from this mesh, rendered and tested on the engine (`load_scene(mesh=...)`).
     `export_level` (the application's `-v`): above 2 the reference's per-view images and clouds are written into `export_dir` (default: `dmap_dir`, else the directory of
     `ply_out` or `mvs_out`) by `export_view_files` -- `depthNNNN.raw.png` before the per-map filters (above 3), the `depthNNNN.*` set after them, `depthNNNN.filtered.*`
@@ -683,7 +699,7 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
         opt = optdense.defaults(); opt.nNumViews = 8; opt.nEstimateNormals = 2
     if mesh_file is not None:
         load_args = dict(load_args, mesh=mesh_file, mesh_engine=engine)
-    sv = load_scene(mvs_in, opt=opt, engine=engine if prepare_on_device else None, **load_args)
+    sv = load_scene(mvs_in, opt=opt, engine=engine if prepare_on_device else None, seed_on_device=seed_on_device, **load_args)
     engine.scene_load(sv, n_levels=int(opt.nSubResolutionLevels))
     export = None
     if export_level > 2:
@@ -697,7 +713,7 @@ def dense_reconstruction(engine, mvs_in: str, mvs_out: str | None = None, opt=No
     compute_depth_maps(engine, sv.ids, opt.params(seed), n_optimize=int(opt.nOptimize), b_filter_adjust=bool(opt.bFilterAdjust), n_speckle_size=int(opt.nSpeckleSize),
                        n_ipol_gap_size=int(opt.nIpolGapSize), f_depth_diff_threshold=float(opt.fDepthDiffThreshold), n_min_views_filter=int(opt.nMinViewsFilter),
                        n_min_views_filter_adjust=int(opt.nMinViewsFilterAdjust), init_depth=sv.init_depth, init_normal=sv.init_normal, scene=sv, dmap_dir=dmap_dir,
-                       image_names=sv.names, export=export)
+                       image_names=sv.names, export=export, seed_mesh=sv.seed_mesh)
     if fusion_mode == 1:
         return sv, None
     cloud = fuse_depth_maps(engine, sv, opt, bgr=sv.bgr)

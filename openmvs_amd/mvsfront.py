@@ -19,13 +19,15 @@ class MVSFOptions(C.Structure):
 _TYPES = {"MVSFViewScore": VIEW_SCORE_DTYPE, "MVSFOptions": MVSFOptions}          # the mirrors by their names in include/mvsfront.h
 _SIGNATURES = _cabi.signatures("mvsfront.h", _TYPES)
 EXPORTS = list(_SIGNATURES)          # every function include/mvsfront.h declares
+_MESH_SIGNATURES = _cabi.signatures("mvsfront_mesh.h", _TYPES)          # ... and its companion header, which mvsfront.h includes
+MESH_EXPORTS = list(_MESH_SIGNATURES)
 _LIB = None
 
 
 def load_library() -> C.CDLL:
     global _LIB
     if _LIB is None:
-        _LIB = _cabi.declare(C.CDLL(_build.build_host_lib("libmvsfront.so")), _SIGNATURES)
+        _LIB = _cabi.declare(_cabi.declare(C.CDLL(_build.build_host_lib("libmvsfront.so")), _SIGNATURES), _MESH_SIGNATURES)
     return _LIB
 
 
@@ -136,6 +138,23 @@ class SceneFront:
         if rc != 0:
             raise ValueError("mvsf_triangulate_depth_map failed: %d" % rc)
         return d, float(dmin.value), float(dmax.value)
+
+    def point_mesh(self, i, points, size, avg_depth=None, normals=True):
+        """mvsf_point_mesh: the mesh `init_depth_map` / `triangulate_depth_map` rasterise (avg_depth not None = with the image corners), as `views.point_mesh` returns it
+        -> (proj (n,2) f32, vert_z (n,) f32, normals (n,3) f32 | None, faces (m,3) uint32, dMin, dMax): the bounds of the points themselves, without the 0.9 / 1.1."""
+        w, h = size
+        p = np.ascontiguousarray(points, np.uint32)
+        nv, nf, dmin, dmax = C.c_int(), C.c_int(), C.c_float(), C.c_float()
+        cap = len(p) + 4                                       # the points and the corners; a planar triangulation of n vertices has fewer than 2 n faces: one call
+        proj = np.zeros((cap, 2), np.float32); z = np.zeros(cap, np.float32); nrm = np.zeros((cap, 3), np.float32) if normals else None
+        faces = np.zeros((2 * cap, 3), np.uint32)
+        rc = self._lib.mvsf_point_mesh(self._h, i, w, h, p, len(p), avg_depth is not None, avg_depth or 0.0, proj, z, nrm, cap, C.byref(nv), faces, 2 * cap, C.byref(nf),
+                                       C.byref(dmin), C.byref(dmax))
+        if rc != 0:
+            raise ValueError("mvsf_point_mesh failed: %d" % rc)
+        proj, z, faces = proj[:nv.value].copy(), z[:nv.value].copy(), faces[:nf.value].copy()
+        nrm = None if nrm is None else nrm[:nv.value].copy()
+        return proj, z, nrm, faces, float(dmin.value), float(dmax.value)
 
 
 def estimate_normal_map(K, depth):

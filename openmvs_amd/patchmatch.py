@@ -81,6 +81,9 @@ _MESH_SIGNATURES = _cabi.signatures("pmhip_mesh.h", _TYPES)
 MESH_EXPORTS = list(_MESH_SIGNATURES)
 _EXPORT_SIGNATURES = _cabi.signatures("pmhip_export.h", _TYPES)
 EXPORT_EXPORTS = list(_EXPORT_SIGNATURES)
+_SEED_SIGNATURES = _cabi.signatures("pmhip_seed.h", _TYPES)
+SEED_EXPORTS = list(_SEED_SIGNATURES)
+SEED_POINTS, SEED_FACES = 0, 1       # include/pmhip_seed.h
 
 _LIB = None
 
@@ -101,6 +104,7 @@ def load_library() -> C.CDLL:
         _cabi.declare(lib, _NORMALS_SIGNATURES, allow_missing=experiment)
         _cabi.declare(lib, _MESH_SIGNATURES, allow_missing=experiment)
         _cabi.declare(lib, _EXPORT_SIGNATURES, allow_missing=experiment)
+        _cabi.declare(lib, _SEED_SIGNATURES, allow_missing=experiment)
         if hasattr(lib, "pmhip_abi_version") and lib.pmhip_abi_version() != PMHIP_ABI_VERSION and not experiment:
             raise RuntimeError("%s has struct layout version %d, these bindings are written for %d (include/pmhip.h)" % (path, lib.pmhip_abi_version(), PMHIP_ABI_VERSION))
         _LIB = lib
@@ -470,6 +474,46 @@ class PatchMatchHIP:
         out = np.zeros(5, np.uint64)
         self._chk(self._lib.pmhip_mesh_get_stats(self._h, out))
         return dict(zip(("batches", "large_faces", "box_pixels", "batch_bytes", "device_us"), (int(v) for v in out)))
+
+    # -- the seed maps of an image's sparse points (include/pmhip_seed.h) ------------------------
+    @staticmethod
+    def _seed_mesh(proj, z, normals, faces):
+        P = np.ascontiguousarray(proj, np.float32).reshape(-1, 2)
+        Z = np.ascontiguousarray(z, np.float32).ravel()
+        N = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        F = np.zeros((0, 3), np.int64) if faces is None else np.asarray(faces).reshape(-1, 3)
+        if len(Z) != len(P) or (N is not None and len(N) != len(P)):
+            raise ValueError("one depth (and one normal) per projected vertex")
+        if len(F) and (F.min() < 0 or F.max() > 0xFFFFFFFF):
+            raise ValueError("face indices must be vertex indices")
+        return P, Z, N, np.ascontiguousarray(F, np.uint32)
+
+    def seed_raster(self, mode, w, h, proj, z, normals=None, faces=None):
+        """The map part of `views.init_depth_map` / `views.triangulate_points_depth_map` on the device (pmhip_seed_raster), host arrays in and out; needs no scene.
+        `mode`: SEED_POINTS (the 2x2 splats of bInitSparse) or SEED_FACES (the faces rasterised in the order given; the highest-numbered face that covers a pixel
+        wins).  -> (depth (h, w), normal (h, w, 3) | None without `normals`), bit for bit the sequential walk."""
+        P, Z, N, F = self._seed_mesh(proj, z, normals, faces)
+        ok = int(w) > 0 and int(h) > 0 and int(w) * int(h) <= 0x7FFFFFFF     # (a refused size reaches the library, which says why; no array is made for it)
+        d = np.zeros((int(h), int(w)) if ok else (1, 1), np.float32)
+        n = None if N is None else np.zeros(d.shape + (3,), np.float32)
+        self._chk(self._lib.pmhip_seed_raster(self._h, int(mode), int(w), int(h), P, Z, N, len(P), F, len(F), d, n))
+        return d, n
+
+    def scene_seed_view(self, idx, mode, proj, z, normals=None, faces=None):
+        """`scene_set_maps(idx, *seed_raster(...))` with only the mesh crossing to the device (pmhip_scene_seed_view): the view's resident depth map, and with `normals`
+        its normal map, at the view's own size."""
+        P, Z, N, F = self._seed_mesh(proj, z, normals, faces)
+        self._chk(self._lib.pmhip_scene_seed_view(self._h, int(idx), int(mode), P, Z, N, len(P), F, len(F)))
+
+    def seed_set_tuning(self, box_pixels=0):
+        """pmhip_seed_set_tuning: faces whose clipped box holds more pixels go to the workgroup route (0 keeps, < 0 restores the default); the maps never depend on it."""
+        self._chk(self._lib.pmhip_seed_set_tuning(self._h, int(box_pixels)))
+
+    def seed_stats(self):
+        """pmhip_seed_get_stats -> {large_faces, device_us, mesh_bytes (of the last call), box_pixels (in force)}."""
+        out = np.zeros(4, np.uint64)
+        self._chk(self._lib.pmhip_seed_get_stats(self._h, out))
+        return dict(zip(("large_faces", "box_pixels", "device_us", "mesh_bytes"), (int(v) for v in out)))
 
     # -- the reference's image and PLY outputs from the resident scene (include/pmhip_export.h) ----
     def x84_threshold(self, values, mul=5.2):

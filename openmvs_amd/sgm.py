@@ -24,6 +24,8 @@ _SIGNATURES = _cabi.signatures("sgmhip.h", _TYPES)
 EXPORTS = list(_SIGNATURES)          # every function include/sgmhip.h declares
 _PLAIN_SIGNATURES = _cabi.signatures("sgmhip_plain.h", _TYPES)          # ... and its companion header, which sgmhip.h includes
 PLAIN_EXPORTS = list(_PLAIN_SIGNATURES)
+_SEED_SIGNATURES = _cabi.signatures("sgmhip_seed.h", _TYPES)
+SEED_EXPORTS = list(_SEED_SIGNATURES)
 _LIB = None
 
 
@@ -37,7 +39,7 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "hipemu_counters") and os.environ.get("OPENMVS_AMD_TEST_EMULATOR") != "1":
             # tests/cpp/hipemu builds of the kernels exist for the CPU test-suite only; the product never computes on the host
             raise RuntimeError("%s is a CPU-emulated test build, not a device library: refusing to load it outside the test-suite" % path)
-        _LIB = _cabi.declare(_cabi.declare(lib, _SIGNATURES), _PLAIN_SIGNATURES)
+        _LIB = _cabi.declare(_cabi.declare(_cabi.declare(lib, _SIGNATURES), _PLAIN_SIGNATURES), _SEED_SIGNATURES)
     return _LIB
 
 
@@ -254,14 +256,49 @@ class SemiGlobalMatcherHIP:
         self._chk(self._lib.sgmhip_rectified_get(self._h, side, b, g, m))
         return b, g, m
 
-    def tsgm_match_rectified(self, min_resolution=320, init_left_disparity=None, n_speckle_size=100, subpixel_mode=SUBPIXEL_LC_BLEND, subpixel_steps=4):
-        """`tsgm_match` on the resident rectified pair of the last `rectify_pair`.  -> (disparity, cost, levels) on the valid grid."""
+    def tsgm_match_rectified(self, min_resolution=320, init_left_disparity=None, n_speckle_size=100, subpixel_mode=SUBPIXEL_LC_BLEND, subpixel_steps=4, seeded=False):
+        """`tsgm_match` on the resident rectified pair of the last `rectify_pair`.  -> (disparity, cost, levels) on the valid grid.
+        `seeded`: the initial left disparity is the resident one of the last `seed_disparity` (sgmhip_tsgm_match_rectified_seeded) and `init_left_disparity` must be None."""
         h, w = self._rect_shape or (6, 6)              # (without a pair the library refuses the call)
-        init = None if init_left_disparity is None else np.ascontiguousarray(init_left_disparity, np.int16)
         d = np.zeros((h - 6, w - 6), np.int16); c = np.zeros((h - 6, w - 6), np.uint16); lv = C.c_int(0)
+        if seeded:
+            if init_left_disparity is not None:
+                raise ValueError("seeded=True reads the resident seed disparity; init_left_disparity must be None")
+            self._chk(self._lib.sgmhip_tsgm_match_rectified_seeded(self._h, min_resolution, n_speckle_size, subpixel_mode, subpixel_steps, self.P1, self.P2s, d, c, C.byref(lv)))
+            self._shape = d.shape
+            return d, c, int(lv.value)
+        init = None if init_left_disparity is None else np.ascontiguousarray(init_left_disparity, np.int16)
         self._chk(self._lib.sgmhip_tsgm_match_rectified(self._h, min_resolution, init, n_speckle_size, subpixel_mode, subpixel_steps, self.P1, self.P2s, d, c, C.byref(lv)))
         self._shape = d.shape
         return d, c, int(lv.value)
+
+    # -- the loop's seed made and kept on the device (include/sgmhip_seed.h) -------------------
+    def seed_raster(self, w, h, proj, z, faces, download=True):
+        """The depth-only `views.triangulate_points_depth_map` from its mesh on the device (sgmhip_seed_raster): the faces rasterised in the order given into a
+        (h, w) depth map that stays resident as the seed.  -> the map, or None without `download`."""
+        P = np.ascontiguousarray(proj, np.float32).reshape(-1, 2); Z = np.ascontiguousarray(z, np.float32).ravel()
+        F = np.asarray(faces).reshape(-1, 3)
+        if len(Z) != len(P):
+            raise ValueError("one depth per projected vertex")
+        if len(F) and (F.min() < 0 or F.max() > 0xFFFFFFFF):
+            raise ValueError("face indices must be vertex indices")
+        F = np.ascontiguousarray(F, np.uint32)
+        ok = int(w) > 0 and int(h) > 0 and int(w) * int(h) <= 0x7FFFFFFF     # (a refused size reaches the library, which says why)
+        out = np.zeros((int(h), int(w)) if ok else (1, 1), np.float32) if download else None
+        self._chk(self._lib.sgmhip_seed_raster(self._h, int(w), int(h), P, Z, len(P), F, len(F), out))
+        return out
+
+    def seed_disparity(self, invH, invQ, subpixelSteps, size, download=True):
+        """`Depth2DisparityMap` of the resident seed (sgmhip_seed_disparity); the (h, w) result stays resident as the initial left disparity of
+        `tsgm_match_rectified(seeded=True)`.  -> the map, or None without `download`."""
+        w, h = size
+        ih = np.ascontiguousarray(invH, np.float64); iq = np.ascontiguousarray(invQ, np.float64)
+        out = np.zeros((int(h), int(w)) if w > 0 and h > 0 else (1, 1), np.int16) if download else None
+        self._chk(self._lib.sgmhip_seed_disparity(self._h, ih, iq, int(subpixelSteps), int(w), int(h), out))
+        return out
+
+    def seed_clear(self):
+        self._chk(self._lib.sgmhip_seed_clear(self._h))
 
     def rectify_stats(self):
         """-> (HIP-event milliseconds of the rectification kernel, its launches) since the last stats_reset(True)."""

@@ -54,7 +54,13 @@ def rectifies_on_device(be):
     return all(hasattr(be, n) for n in ("scene_set_images", "rectify_pair", "tsgm_match_rectified")) and bool(getattr(be, "rectify_on_device", True))
 
 
-def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, subpixel_steps=4, seed_depth=None, image_ids=None):
+def seeds_on_device(be):
+    """The backend rasterises the seed from its mesh, converts it and hands it to the loop on the device (`SemiGlobalMatcherHIP.seed_raster` / `seed_disparity` /
+    `tsgm_match_rectified(seeded=True)`), and was not told to leave that to the host (`DeviceBackend(..., seed_on_device=False)`)."""
+    return rectifies_on_device(be) and all(hasattr(be, n) for n in ("seed_raster", "seed_disparity")) and bool(getattr(be, "seed_on_device", False))
+
+
+def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, subpixel_steps=4, seed_depth=None, image_ids=None, seed_mesh=None):
     """One pair of `Match(scene, ...)`: cam = (K, R, C).  Returns the `.dimap` content: dict(disparity, cost, H, Q, image_size, subpixel_steps)
     or None if the pair cannot be rectified.
 
@@ -62,6 +68,10 @@ def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, su
     `TriangulatePoints2DepthMap(..., bAddCorners = true)` (SemiGlobalMatcher.cpp:608-618; `views.triangulate_points_depth_map` or
     `mvsf_triangulate_depth_map`); it becomes the first level's initial disparities through Depth2DisparityMap (`:619-625`).  Without it the
     first level searches the default range around zero.
+
+    seed_mesh: callable (w, h) -> (proj, z, faces), the mesh that depth map is rasterised from (`views.triangulate_points` with corners: z the depth of every
+    vertex).  With it, a resident pair (`image_ids`) and a backend that seeds on the device (`seeds_on_device`) the seed is rasterised, converted and consumed there
+    and no map crosses to the host; otherwise `seed_depth` is used as before.  Both routes give the same result.
 
     image_ids: (a, b), the slots of the two images in the backend's resident scene (`be.scene_set_images`).  With them and a backend that
     rectifies (`rectifies_on_device`) the pair is warped, converted to gray and matched on the device and no image travels; otherwise the host
@@ -79,7 +89,15 @@ def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, su
     f = 1 << k
     w, h = r["size"][0] // f * f, r["size"][1] // f * f           # the loop's 8-bit resampler wants multiples of 2^levels: crop right / bottom
     init = None
-    if seed_depth is not None:
+    seeded = on_device and seed_mesh is not None and seeds_on_device(be)
+    if seeded:
+        s = 0.5 / f
+        sw, sh = compute_resize((bgrA.shape[1], bgrA.shape[0]), s)
+        be.seed_raster(sw, sh, *seed_mesh(sw, sh), download=False)
+        H2, Q2 = rectify.scale_stereo_rectification(H, r["Q"], s)
+        hw, hh = compute_resize((w // f, h // f), 0.5)
+        be.seed_disparity(np.linalg.inv(H2), np.linalg.inv(Q2), 1, (hw - 2 * tsgm.HW, hh - 2 * tsgm.HW), download=False)
+    elif seed_depth is not None:
         s = 0.5 / f                                               # scale * 0.5
         depth = seed_depth(*compute_resize((bgrA.shape[1], bgrA.shape[0]), s))
         H2, Q2 = rectify.scale_stereo_rectification(H, r["Q"], s)
@@ -87,8 +105,11 @@ def match_pair(be, bgrA, camA, bgrB, camB, shared_points, min_resolution=320, su
         init = be.Depth2DisparityMap(depth, np.linalg.inv(H2), np.linalg.inv(Q2), 1, (hw - 2 * tsgm.HW, hh - 2 * tsgm.HW))
     if on_device:                                                 # sgmhip_rectify_pair + sgmhip_tsgm_match_rectified: the crop leaves the pixel coordinates as they are
         be.rectify_pair(image_ids[0], image_ids[1], np.linalg.inv(r["H1"]), np.linalg.inv(r["H2"]), (w, h), _srgb_table())
-        disp, cost, _ = be.tsgm_match_rectified(min_resolution=min_resolution, init_left_disparity=init, subpixel_steps=subpixel_steps)
-        return dict(disparity=disp, cost=cost, H=H, Q=r["Q"], image_size=(bgrA.shape[1], bgrA.shape[0]), subpixel_steps=subpixel_steps, seeded=init is not None)
+        if seeded:
+            disp, cost, _ = be.tsgm_match_rectified(min_resolution=min_resolution, subpixel_steps=subpixel_steps, seeded=True)
+        else:
+            disp, cost, _ = be.tsgm_match_rectified(min_resolution=min_resolution, init_left_disparity=init, subpixel_steps=subpixel_steps)
+        return dict(disparity=disp, cost=cost, H=H, Q=r["Q"], image_size=(bgrA.shape[1], bgrA.shape[0]), subpixel_steps=subpixel_steps, seeded=seeded or init is not None)
     lb, rb = r["rect1"][:h, :w].copy(), r["rect2"][:h, :w].copy()
     args = (lb, to_gray_linear(lb), rb, to_gray_linear(rb), r["mask1"][:h, :w].copy(), r["mask2"][:h, :w].copy())
     if hasattr(be, "tsgm_match"):                                 # the device runs the whole loop in one resident call (sgmhip_tsgm_match)
@@ -167,7 +188,8 @@ def match_scene(be, sc, cams, bgr, neighbors, out_dir, n_views=0, f_min_score_ra
     each image against its listed neighbours -- a pair whose disparity file exists already, in either order, is skipped (:543-545) -- rectified, matched through the tSGM
     loop seeded from the image's sparse points (`match_pair`), written as `<left>_<right>.dimap`.
     sc: mvsi.Scene; cams: views.Cameras; bgr: the colour images; neighbors: {image: its whole scored list (Image::neighbors)}; avg_depth: {image: Image::avgDepth} for the
-    seed's corner points.  Returns the pairs written."""
+    seed's corner points.  The seed's mesh (`views.triangulate_points`) is built once per (image, size) and reused for all of that image's pairs; a backend that
+    seeds on the device (`seeds_on_device`) gets the mesh, any other the depth map rasterised from it on the host.  Returns the pairs written."""
     import os
     from . import dmap, views
     os.makedirs(out_dir, exist_ok=True)
@@ -183,7 +205,9 @@ def match_scene(be, sc, cams, bgr, neighbors, out_dir, n_views=0, f_min_score_ra
     listed = {i: _listed(neighbors[i], n_views, f_min_score_ratio, f_min_score) for i in sorted(neighbors)}
     resident = False                                             # the images this run touches are in the backend's scene (uploaded before the first pair, once)
     done = []
+    meshes, depths = {}, {}                                      # (image, w, h) -> the seed's mesh / the depth map rasterised from it on the host
     for i in sorted(neighbors):
+        meshes.clear(); depths.clear()                           # (an image's pairs follow one another)
         for j in listed[i]:
             if os.path.exists(os.path.join(out_dir, pair_file_name(i, j))) or os.path.exists(os.path.join(out_dir, pair_file_name(j, i))):
                 continue
@@ -193,13 +217,23 @@ def match_scene(be, sc, cams, bgr, neighbors, out_dir, n_views=0, f_min_score_ra
                 resident = True
             pts = np.nonzero(sees(i))[0]
 
-            def seed(w, h, i=i, pts=pts):
-                K, R, C, _, _ = sc.camera(i, (w, h))
-                P = K @ np.hstack([R, -(R @ C)[:, None]])
-                return views.triangulate_points_depth_map(K, P, sc.vertices[pts], w, h, avg_depth=None if avg_depth is None else avg_depth[i])[0]
+            def mesh(w, h, i=i, pts=pts):
+                if (i, w, h) not in meshes:
+                    K, R, C, _, _ = sc.camera(i, (w, h))
+                    P = K @ np.hstack([R, -(R @ C)[:, None]])
+                    proj, _, vert, faces = views.triangulate_points(K, P, sc.vertices[pts], w, h, None if avg_depth is None else avg_depth[i])
+                    meshes[(i, w, h)] = (proj, np.ascontiguousarray(vert[:, 2]), faces)
+                return meshes[(i, w, h)]
 
+            def seed(w, h, i=i):
+                if (i, w, h) not in depths:
+                    proj, z, faces = mesh(w, h)
+                    depths[(i, w, h)] = views.raster_faces_depth_map(proj, z, faces, w, h)
+                return depths[(i, w, h)]
+
+            with_seed = avg_depth is not None and len(pts) >= 3
             p = match_pair(be, bgr[i], cam(i), bgr[j], cam(j), sc.vertices[sees(i) & sees(j)], min_resolution=min_resolution, subpixel_steps=subpixel_steps,
-                           seed_depth=seed if (avg_depth is not None and len(pts) >= 3) else None, image_ids=(i, j) if resident else None)
+                           seed_depth=seed if with_seed else None, image_ids=(i, j) if resident else None, seed_mesh=mesh if with_seed else None)
             if p is None:
                 continue                                         # the pair cannot be rectified (:566-567)
             dmap.save_dimap(os.path.join(out_dir, pair_file_name(i, j)), p["image_size"], p["H"], p["Q"], p["subpixel_steps"], p["disparity"], p["cost"])
@@ -250,10 +284,12 @@ class DeviceBackend:
     """The device behind `match_pair` / `fuse_pairs`: `sgm.SemiGlobalMatcherHIP` has every step of the interface (and the resident loop and fusion, `tsgm_match`,
     `fuse_disparities`) except the float area resampler of the image pyramid, which the PatchMatch library provides (`PatchMatchHIP.resize`).
     rectify_on_device: keep the scene's images resident and rectify every pair on the device (`match_scene`, `match_pair`); False leaves the warps and the gray
-    conversion to the host and uploads each pair's images for the loop -- the same results, for A/B runs and tests."""
+    conversion to the host and uploads each pair's images for the loop -- the same results, for A/B runs and tests.
+    seed_on_device: the loop's seed is rasterised from its mesh, converted to disparities and consumed on the device (`seeds_on_device`; it needs the resident pair, so
+    it follows `rectify_on_device`); False rasterises on the host and uploads the disparities -- the same bits."""
 
-    def __init__(self, matcher, engine, rectify_on_device=True):
-        self.m, self.e, self.rectify_on_device = matcher, engine, bool(rectify_on_device)
+    def __init__(self, matcher, engine, rectify_on_device=True, seed_on_device=True):
+        self.m, self.e, self.rectify_on_device, self.seed_on_device = matcher, engine, bool(rectify_on_device), bool(seed_on_device)
 
     def resize_area_f32(self, img, f):
         return self.e.resize(0, img, f)

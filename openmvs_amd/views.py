@@ -273,9 +273,40 @@ def init_depth_map(scene: mvsi.Scene, cams: Cameras, ID: int, points: np.ndarray
             if y1 >= y0 and x1 >= x0:                                    # (a projection outside the image splats nothing)
                 depthMap[y0:y1 + 1, x0:x1 + 1] = z
         return depthMap, normalMap, float(d.min() * f32(0.9)), float(d.max() * f32(1.1))
+    proj, z, vz, normals, faces, dMin, dMax = point_mesh(scene, cams, ID, points, opt, avg_depth)
+    if not opt.bInitSparse:
+        if not len(faces):                                                                 # no face: nothing is rasterised
+            return depthMap, normalMap, dMin, dMax
+        # dense interpolation, DepthMap.cpp:1158-1190: rasterise every mesh face (TImage::RasterizeTriangleBary, libs/Common/Types.inl:2629-2669) with
+        # perspective-correct barycentric depth and normal.  Faces in a canonical order (the reference's is CGAL's; only pixels exactly on a shared edge see it).
+        for fa in faces:
+            _raster_face(proj[fa], vz[fa], normals[fa], depthMap, normalMap)
+        return depthMap, normalMap, dMin, dMax
+    ix = np.floor(proj).astype(np.int64)
+    for (x, y), zz, n in zip(ix, vz, normals):
+        for dx, dy in ((0, 0), (1, 0), (0, 1), (1, 1)):
+            ax, ay = x + dx, y + dy
+            if 0 <= ax < w and 0 <= ay < h:
+                depthMap[ay, ax] = zz
+                normalMap[ay, ax] = n
+    return depthMap, normalMap, dMin, dMax
+
+
+def point_mesh(scene: mvsi.Scene, cams: Cameras, ID: int, points: np.ndarray, opt: DenseOptions = DenseOptions(), avg_depth=None):
+    """The mesh part of `init_depth_map`: what `TriangulatePoints2DepthMap` rasterises, before it does (DepthMap.cpp:1117-1138) -- the input of the device rasteriser
+    (`PatchMatchHIP.seed_raster` / `scene_seed_view`, csrc/seed_raster.hip).
+
+    -> (proj (n,2) f32, z (n_points,) f32 depths of the points, vert_z (n,) f32 depth of every vertex (with `bAddCorners` the four corners follow the points),
+    normals (n,3) f32 area-weighted vertex normals, faces (m,3) int64 in the canonical order of `triangulate_points`, dMin, dMax as `init_depth_map` returns them).
+    No points: empty arrays and the range [0.1, 100].  `nMinViewsTrustPoint < 2` has no mesh (the 5x5 splat of `init_depth_map`)."""
+    if opt.nMinViewsTrustPoint < 2:
+        raise ValueError("nMinViewsTrustPoint < 2 splats the points and triangulates nothing")
+    if len(points) == 0:
+        return np.zeros((0, 2), f32), np.zeros(0, f32), np.zeros(0, f32), np.zeros((0, 3), f32), np.zeros((0, 3), np.int64), 1e-1, 1e+2
     if opt.bAddCorners and avg_depth is None:
         raise ValueError("bAddCorners needs the image's average depth (select_neighbor_views returns it)")
-    proj, z, vert, faces = triangulate_points(K, cams.P[ID], X, w, h, avg_depth if opt.bAddCorners else None)
+    w, h = (int(v) for v in cams.size[ID])
+    proj, z, vert, faces = triangulate_points(cams.K[ID], cams.P[ID], scene.vertices[points], w, h, avg_depth if opt.bAddCorners else None)
     normals = np.zeros_like(vert)
     if len(faces):
         f0, f1, f2 = faces[:, 0], faces[:, 1], faces[:, 2]
@@ -286,22 +317,7 @@ def init_depth_map(scene: mvsi.Scene, cams: Cameras, ID: int, points: np.ndarray
         inv = np.where(nrm > 0, 1.0 / np.maximum(nrm, 1e-300), 0.0)          # cv::normalize: v * (1/|v|), the norm in double
         normals = (normals.astype(np.float64) * inv[:, None]).astype(f32)
     dMin, dMax = float(z.min() * f32(0.9)), float(z.max() * f32(1.1))            # the corners do not count (depthBounds, DepthMap.cpp:1043-1046)
-    if not opt.bInitSparse:
-        if not len(faces):                                                                 # no face: nothing is rasterised
-            return depthMap, normalMap, dMin, dMax
-        # dense interpolation, DepthMap.cpp:1158-1190: rasterise every mesh face (TImage::RasterizeTriangleBary, libs/Common/Types.inl:2629-2669) with
-        # perspective-correct barycentric depth and normal.  Faces in a canonical order (the reference's is CGAL's; only pixels exactly on a shared edge see it).
-        for fa in faces:
-            _raster_face(proj[fa], vert[fa, 2], normals[fa], depthMap, normalMap)
-        return depthMap, normalMap, dMin, dMax
-    ix = np.floor(proj).astype(np.int64)
-    for (x, y), zz, n in zip(ix, vert[:, 2], normals):
-        for dx, dy in ((0, 0), (1, 0), (0, 1), (1, 1)):
-            ax, ay = x + dx, y + dy
-            if 0 <= ax < w and 0 <= ay < h:
-                depthMap[ay, ax] = zz
-                normalMap[ay, ax] = n
-    return depthMap, normalMap, dMin, dMax
+    return proj, z, np.ascontiguousarray(vert[:, 2]), normals, faces, dMin, dMax
 
 
 def triangulate_points(K, P, X, w, h, avg_depth=None):
@@ -384,9 +400,17 @@ def triangulate_points_depth_map(K, P, X, w, h, avg_depth=None, sparse=False):
                 if 0 <= x + dx < w and 0 <= y + dy < h:
                     depthMap[y + dy, x + dx] = zz
     else:
-        for fa in faces:
-            _raster_face(proj[fa], vert[fa, 2], None, depthMap, None)
+        depthMap = raster_faces_depth_map(proj, vert[:, 2], faces, w, h)
     return depthMap, (float(z.min()) if len(z) else 3.4028234663852886e+38), (float(z.max()) if len(z) else 0.0)
+
+
+def raster_faces_depth_map(proj, z, faces, w, h):
+    """The face loop of the depth-only `TriangulatePoints2DepthMap` (DepthMap.cpp:1225-1249) over a mesh (`triangulate_points`: z the depth of every vertex): the
+    faces in the order given, a later one overwriting an earlier one -- what `SemiGlobalMatcherHIP.seed_raster` computes on the device."""
+    depthMap = np.zeros((h, w), f32)
+    for fa in faces:
+        _raster_face(proj[fa], z[fa], None, depthMap, None)
+    return depthMap
 
 
 def _raster_face(v, zs, ns, depthMap, normalMap):
