@@ -27,7 +27,8 @@ struct alignas(16) PMPix {
 	float p0, p1, scaleRange, depthRange;      // refinement state (:828-852)
 	int st, it, idxScale, flags;               // flags: bit 0 smooth, bit 1 changed, bit 2 / 3 propagation candidate 0 / 1 exists, bits 8..11 closeMask
 	float hd, hnx, hny, hnz, hp0, hp1;         // hypothesis being scored
-	int hst, pad0;
+	int hst;
+	float hdd;                                 // ... and its distance to the pixel's low-resolution prior, min(|prior - hd| / prior, 0.5): the view-independent term of the prior blend
 	float qX[4][3], qn[4][3];                  // neighborsClose: point and normal of slot k
 	float vx, vy, normSq0, sumW;
 	double X0x, X0y;
@@ -58,7 +59,7 @@ enum { PMF_SMOOTH = 1, PMF_CHANGED = 2, PMF_POK0 = 4, PMF_POK1 = 8 };
 // neighbour slots (bounds tests, coordinates, map indices).  afterPatch() runs once the visit's loads have been waited for (the band kernel publishes its
 // previous step there).  Result: r* = what the maps hold at this pixel after the visit, wr = it changed.
 template <int G, int VPL, bool GEO, bool BUF, bool TILED>
-__device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, const PMImgBuf& rs, uint32_t pass, int sgn, float2* s_wg, PMPix* s_pixg, const double* hotBase,
+__device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, const PMImgBuf& rs, const PMLvl& lv, uint32_t pass, int sgn, float2* s_wg, PMPix* s_pixg, const double* hotBase,
 		int g, int v, bool active, int x, int y, int ySafe, size_t idx, const bool* bok, const int* qxs, const int* qys, const size_t* qis, unsigned oldMask,
 		float n0D, float n0N0, float n0N1, float n0N2, float n0C, float n1D, float n1N0, float n1N1, float n1N2, float n1C,
 		float& rD, float& rN0, float& rN1, float& rN2, float& rC, bool& wr PM_PROF_ARG) {
@@ -217,6 +218,10 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 				P->st = st; P->it = (int)it; P->idxScale = (int)idxScale; P->flags = flags;
 				P->scaleRange = scaleRange; P->depthRange = depthRange; P->p0 = p0; P->p1 = p1;
 				P->hd = hd; P->hnx = hnx; P->hny = hny; P->hnz = hnz; P->hp0 = hp0; P->hp1 = hp1; P->hst = hst;
+				if (t.prior) {   // (a level without a prior never reads it)
+					const float pr = s_wg[PM_NT].x;
+					P->hdd = (need && pr > 0) ? pm_prior_delta(pr, hd) : 0.f;
+				}
 			}
 		}
 		const unsigned long long needBal = __ballot(need);
@@ -274,9 +279,9 @@ __device__ __forceinline__ void pm_visit(const PMTask& t, const PMKParams& kp, c
 					PM_CENSUS_VIEW(t.w, G, u);
 					float s1;
 					if constexpr (GEO) s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, 1.f, 1.f, 1.f, 1.f, 0.f,
-						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P), greq, u, VPL);
+						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P), greq, u, VPL, BUF ? &lv : nullptr, (const float*)&P->hdd);
 					else s1 = pm_score_view<GEO, BUF ? 2 : 1, true, true>(t.src[vw], t, kp, P->x, P->y, P->X0x, P->X0y, P->normSq0, P->sumW, s_wg, hd, hnx, hny, hnz, 1.f, 1.f, 1.f, 1.f, 0.f,
-						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P));
+						hotBase + vw * NBD, hotBase + vw * NBD + PM_SRC_HOT, rs PM_PROF_PASS, (const double*)P->hr, (const float*)pm_pix_sf((PM_LDS PMPix*)P), nullptr, 0, 1, BUF ? &lv : nullptr, (const float*)&P->hdd);
 					PM_CENSUS_VIEW_END();
 					if (s1 < sc) { sc2 = sc; sc = s1; } else if (s1 < sc2) sc2 = s1;
 				}
@@ -332,6 +337,7 @@ __global__ __launch_bounds__(64, (GEO ? PM_BAND_MINWAVES : PM_BAND_MINWAVES_PHOT
 	}
 	const PMTask& t = tasks[vby];
 	const PMImgBuf rs = pm_make_imgbuf(t);
+	const PMLvl lv = BUF ? pm_make_lvl(t) : PMLvl();
 	const int lane = threadIdx.x;
 	for (int i = lane; i < NV * NBD; i += 64) {
 		double e = ((const double*)&t.src[i / NBD])[i % NBD];
@@ -375,8 +381,13 @@ __global__ __launch_bounds__(64, (GEO ? PM_BAND_MINWAVES : PM_BAND_MINWAVES_PHOT
 	}
 	__syncthreads();
 	float rD, rN0, rN1, rN2, rC; bool wr;
-	pm_visit<G, VPL, GEO, BUF, TILED>(t, kp, rs, pass, sgn, s_w[g], &s_pix[g], s_src, g, v, active, x, y, active ? y : PM_HW, active ? idx : (size_t)PM_HW * w + PM_HW, bok, qxs, qys, qis, sp.oldMask,
+	pm_visit<G, VPL, GEO, BUF, TILED>(t, kp, rs, lv, pass, sgn, s_w[g], &s_pix[g], s_src, g, v, active, x, y, active ? y : PM_HW, active ? idx : (size_t)PM_HW * w + PM_HW, bok, qxs, qys, qis, sp.oldMask,
 		n0D, n0N0, n0N1, n0N2, n0C, n1D, n1N0, n1N1, n1N2, n1C, rD, rN0, rN1, rN2, rC, wr PM_PROF_PASS);
-	if (wr && v == 0) { gDepth[idx] = rD; gNormal[idx * 3] = rN0; gNormal[idx * 3 + 1] = rN1; gNormal[idx * 3 + 2] = rN2; gConf[idx] = rC; }
+	if (wr && v == 0) {
+		// (the pixel's position again, from the state lane row 0 wrote at the head of the visit: its map index does not wait in two registers across the visit)
+		const PM_LDS PMPix* P = pm_launder(&s_pix[g]);
+		const size_t io = (size_t)P->y * w + P->x;
+		gDepth[io] = rD; gNormal[io * 3] = rN0; gNormal[io * 3 + 1] = rN1; gNormal[io * 3 + 2] = rN2; gConf[io] = rC;
+	}
 	PM_PROF_FLUSH();
 }

@@ -183,6 +183,23 @@ __device__ __forceinline__ bool pm_inside1(float px, float py, int w, int h) {
 	return px >= 1.f && py >= 1.f && px <= (float)(w - 2) && py <= (float)(h - 2);
 }
 __device__ __forceinline__ bool pm_in_range(float d, float lo, float hi) { return lo <= d && d < hi; } // ISINSIDE, Types.h:1193
+// What a patch evaluation needs of its source image's size: the size, the bounds of pm_inside1 and the thresholds of the corner verdict (pm_score_view (2), (3)),
+// formed by the float operations named here and nowhere else.  pm_sweep2_kernel and the init kernel on the level's quad buffer (BUF / MODE 2: every source has the level's
+// size) form them once per wave, into scalar registers (pm_make_lvl); a source with its own size, and the speculative kernels, form them per evaluation from the view's hot block.
+struct PMLvl {
+	int sw, sh;
+	float xm, ym;       // (float)(sw - 2), (float)(sh - 2)
+	float oneD;         // 1 + delta, delta = 2^-17 max(sw, sh)
+	float xmD, ymD;     // xm - delta, ym - delta
+};
+__device__ __forceinline__ PMLvl pm_lvl_of(int sw, int sh) {
+	PMLvl l;
+	l.sw = sw; l.sh = sh; l.xm = (float)(sw - 2); l.ym = (float)(sh - 2);
+	const float delta = (float)max(sw, sh) * 7.62939453125e-06f;   // 2^-17
+	l.oneD = 1.f + delta; l.xmD = l.xm - delta; l.ymD = l.ym - delta;
+	return l;
+}
+__device__ __forceinline__ bool pm_inside1(float px, float py, const PMLvl& l) { return px >= 1.f && py >= 1.f && px <= l.xm && py <= l.ym; }   // pm_inside1(px, py, l.sw, l.sh)
 
 // Dir2Normal / Normal2Dir, libs/Common/Util.inl:754-766
 __device__ __forceinline__ void pm_dir2normal(float p0, float p1, float& nx, float& ny, float& nz) {
@@ -526,6 +543,20 @@ __device__ __forceinline__ PMImgBuf pm_make_imgbuf(const PMTask& t) {
 	b.rs = pm_make_rsrc(t.qArr, t.qCount);
 	return b;
 }
+// the size block of a launch that gathers from the level's quad buffer: every source view has the size of the first, wave-uniform (one task per workgroup)
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ int pm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+#else
+__device__ __forceinline__ int pm_uniform(int v) { return v; }
+#endif
+__device__ __forceinline__ float pm_uniform(float v) { return pm_u2f((uint32_t)pm_uniform(pm_f2i(v))); }
+__device__ __forceinline__ PMLvl pm_make_lvl(const PMTask& t) {
+	const PMLvl l = pm_lvl_of(t.src[0].w, t.src[0].h);
+	PMLvl u;
+	u.sw = pm_uniform(l.sw); u.sh = pm_uniform(l.sh); u.xm = pm_uniform(l.xm); u.ym = pm_uniform(l.ym);
+	u.oneD = pm_uniform(l.oneD); u.xmD = pm_uniform(l.xmD); u.ymD = pm_uniform(l.ymD);
+	return u;
+}
 
 // One tap row (5 taps) of ScorePixelImage through global loads, with the reference's per-tap tests; from the row-major image (QUAD = false) or from the view's
 // anti-diagonal-major quad image read as plain floats (QUAD = true: the clamped position's entry (lx + ly) * sh + ly holds exactly the four texels of the sample).
@@ -593,11 +624,16 @@ __device__ __forceinline__ void pm_range_corner(PMTapRange& rg, float px, float 
 // positions of a row's five taps, their samples requested; nothing waits here.  CORNERS: the row is the patch's first one -- its taps 0 and 4 are recorded (the last row's
 // are recorded by pm_taps_fast from the positions the row leaves behind, so that the loop over the rows has one body).
 // Entry index of sample (lx, ly) of the view whose image starts at entry qbase: qbase + (lx + ly) * sh + ly == lx * sh + (ly * (sh + 1) + qbase): two v_mad_u32_u24.
-template <bool BUF, bool CORNERS>
-__device__ __forceinline__ void pm_row_issue(const PMImgBuf& rs, unsigned qbase, const pm_gcf4 imgQ, int sw, int sh, float h0, float h3, float h6, float X0, float X1, float X2,
-		PMRowPos& p, PMRowQ& q, PMTapRange& rg)
+// EARLY (with CORNERS): between the positions and the loads, the row's taps 0 and 4 -- the patch corners (0,0) and (0,4) -- are tested as the reference tests a tap; true =
+// one of them lies outside the image, nothing was requested (pm_score_view).  `early` = the start values are sane (pm_score_view), so that a corner whose z lies inside
+// [2^-40, 2^40] has the IEEE quotients (pm_div2_inrange); a corner whose z does not decides nothing.
+template <bool BUF, bool CORNERS, bool EARLY = false>
+__device__ __forceinline__ bool pm_row_issue(const PMImgBuf& rs, unsigned qbase, const pm_gcf4 imgQ, const PMLvl& lv, float h0, float h3, float h6, float X0, float X1, float X2,
+		PMRowPos& p, PMRowQ& q, PMTapRange& rg, bool early = false)
 {
+	const int sw = lv.sw, sh = lv.sh;
 	unsigned idx[5];
+	bool outside = false;
 #pragma unroll
 	for (int j = 0; j < 5; ++j) {
 		pm_div2_inrange(X0, X1, X2, &p.ptx[j], &p.pty[j]);
@@ -605,8 +641,15 @@ __device__ __forceinline__ void pm_row_issue(const PMImgBuf& rs, unsigned qbase,
 		if (BUF) idx[j] = pm_mad24(lx, sh, pm_mad24(ly, sh + 1, qbase));
 		else { const int lxc = min(max(lx, 0), sw - 2), lyc = min(max(ly, 0), sh - 2); idx[j] = (unsigned)(lxc + lyc) * (unsigned)sh + (unsigned)lyc; }
 		if (CORNERS && (j == 0 || j == 4)) pm_range_corner(rg, p.ptx[j], p.pty[j], X2);
+#ifdef PM_PROBE_EVAL_TRIM
+		if (CORNERS && EARLY && j == 0)   // measurement builds only (profiles/eval_trim_bound.log): the near corner alone
+#else
+		if (CORNERS && EARLY && (j == 0 || j == 4))
+#endif
+			outside = outside || (X2 >= 9.094947e-13f && X2 <= 1.0995116e12f && !pm_inside1(p.ptx[j], p.pty[j], lv));
 		X0 += h0; X1 += h3; X2 += h6;
 	}
+	if (CORNERS && EARLY && early && outside) return true;
 #if defined(PM_PROBE_WIDEN_QUAD_BLOCK) && defined(__HIP_DEVICE_COMPILE__)
 	if (BUF && rs.oneBlock) {
 #pragma unroll
@@ -615,6 +658,7 @@ __device__ __forceinline__ void pm_row_issue(const PMImgBuf& rs, unsigned qbase,
 #endif
 	if (BUF) pm_bufload5(q.q0, q.q1, q.q2, q.q3, q.q4, idx[0], idx[1], idx[2], idx[3], idx[4], rs.rs);
 	else { q.q0 = pm_loadq(imgQ, idx[0]); q.q1 = pm_loadq(imgQ, idx[1]); q.q2 = pm_loadq(imgQ, idx[2]); q.q3 = pm_loadq(imgQ, idx[3]); q.q4 = pm_loadq(imgQ, idx[4]); }
+	return false;
 }
 // the row's samples have arrived (LEFT younger loads may still be under way): bilinear values and the three running sums, in the reference's order
 template <bool BUF, int LEFT>
@@ -639,23 +683,24 @@ __device__ __forceinline__ void pm_row_consume(const PMRowPos& p, PMRowQ& q, con
 // The 25 taps of a patch as a two-deep software pipeline over its five rows: the samples of row i + 1 are requested before row i is consumed, so a wave has ten
 // 16-byte loads in flight instead of five and waits for memory three times per patch instead of five (a wave-visit is a chain of ~80 such round trips and the launch
 // of a diagonal lasts as long as one wave-visit: DESIGN.md 4.2).  Two register sets (A, B) alternate; the rows are written out so that no set is ever copied.
-template <bool BUF>
-__device__ __forceinline__ void pm_taps_fast(const PMImgBuf& rs, unsigned qbase, const pm_gcf4 imgQ, int sw, int sh, const float* H, float bX0, float bX1, float bX2,
-		const float2* wts, float& sum, float& sumSq, float& num, PMTapRange& rg)
+// EARLY: returns true, with nothing requested and nothing summed, if a corner of the first row lies outside the image (pm_row_issue).
+template <bool BUF, bool EARLY>
+__device__ __forceinline__ bool pm_taps_fast(const PMImgBuf& rs, unsigned qbase, const pm_gcf4 imgQ, const PMLvl& lv, const float* H, float bX0, float bX1, float bX2,
+		const float2* wts, float& sum, float& sumSq, float& num, PMTapRange& rg, bool early)
 {
 	PMRowPos pa, pb; PMRowQ qa, qb;
-	pm_row_issue<BUF, true>(rs, qbase, imgQ, sw, sh, H[0], H[3], H[6], bX0, bX1, bX2, pa, qa, rg);
+	if (pm_row_issue<BUF, true, EARLY>(rs, qbase, imgQ, lv, H[0], H[3], H[6], bX0, bX1, bX2, pa, qa, rg, early)) return true;
 	// rows (0,1), (2,3) as one loop body with the A / B sets swapping roles (no copies), then row 4.  The scheduling barriers keep the compiler from pulling the next
 	// row's divisions above the current row's arithmetic (which is what it does with the whole patch unrolled: every position of the patch live at once, 600 B of scratch)
 #pragma unroll 1
 	for (int i = 0; i < 4; i += 2) {
 		bX0 += H[1]; bX1 += H[4]; bX2 += H[7];
-		pm_row_issue<BUF, false>(rs, qbase, imgQ, sw, sh, H[0], H[3], H[6], bX0, bX1, bX2, pb, qb, rg);
+		pm_row_issue<BUF, false>(rs, qbase, imgQ, lv, H[0], H[3], H[6], bX0, bX1, bX2, pb, qb, rg);
 		PM_SCHED_BARRIER();
 		pm_row_consume<BUF, 5>(pa, qa, wts + i * 5, sum, sumSq, num);
 		PM_SCHED_BARRIER();
 		bX0 += H[1]; bX1 += H[4]; bX2 += H[7];
-		pm_row_issue<BUF, false>(rs, qbase, imgQ, sw, sh, H[0], H[3], H[6], bX0, bX1, bX2, pa, qa, rg);
+		pm_row_issue<BUF, false>(rs, qbase, imgQ, lv, H[0], H[3], H[6], bX0, bX1, bX2, pa, qa, rg);
 		PM_SCHED_BARRIER();
 		pm_row_consume<BUF, 5>(pb, qb, wts + (i + 1) * 5, sum, sumSq, num);
 		PM_SCHED_BARRIER();
@@ -664,6 +709,7 @@ __device__ __forceinline__ void pm_taps_fast(const PMImgBuf& rs, unsigned qbase,
 	pm_range_corner(rg, pa.ptx[0], pa.pty[0], bX2);
 	pm_range_corner(rg, pa.ptx[4], pa.pty[4], (((bX2 + H[6]) + H[6]) + H[6]) + H[6]);
 	pm_row_consume<BUF, 0>(pa, qa, wts + 20, sum, sumSq, num);
+	return false;
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
@@ -674,6 +720,11 @@ __device__ __forceinline__ void pm_taps_fast(const PMImgBuf& rs, unsigned qbase,
 inline unsigned long long pm_tap_census[2][4];
 extern "C" __attribute__((visibility("default"))) void pm_debug_tap_census(unsigned long long out[8], int reset) {
 	for (int i = 0; i < 8; ++i) { if (out) out[i] = pm_tap_census[i / 4][i % 4]; if (reset) pm_tap_census[i / 4][i % 4] = 0; }
+}
+// ... and, of the optimistic evaluations, those the verdict after the gather found outside the image (thRobust): [0] init kernel, [1] sweep kernels
+inline unsigned long long pm_tap_census_outside[2];
+extern "C" __attribute__((visibility("default"))) void pm_debug_tap_census_outside(unsigned long long out[2], int reset) {
+	for (int i = 0; i < 2; ++i) { if (out) out[i] = pm_tap_census_outside[i]; if (reset) pm_tap_census_outside[i] = 0; }
 }
 #endif
 // ---- the geometric term's gather (DepthMap.cpp:535-551) --------------------------------------------------------------------------------------------------------
@@ -767,6 +818,9 @@ __device__ __forceinline__ float pm_geo_consistency(float x1x, float x1y, float 
 	return consistency;
 }
 
+// the prior blend's distance term (DepthMap.cpp:553-561), prior > 0
+__device__ __forceinline__ float pm_prior_delta(float prior, float depth) { return pm_minf(pm_fabsf(prior - depth) / prior, 0.5f); }
+
 // ScorePixelImage for this lane's source view, DepthMap.cpp:465-564.
 // sf0..3: the (view-independent) smoothness factors of the up-to-4 close neighbours, in insertion order; exactly 1.f for a neighbour that does not exist or does
 // not take part (DepthMap.cpp:524-533).
@@ -777,17 +831,22 @@ __device__ __forceinline__ float pm_geo_consistency(float x1x, float x1y, float 
 // sfp: where the four factors are read from instead, at the point where the score takes them (16-byte aligned).
 // hot / geoTab: the hot and geometric blocks of `s` (PMSrcView), in HBM (init kernel) or in the wave's LDS copy (sweep kernels); the image size and the view's
 // first entry in the level's quad buffer travel with the homography entries.
-// EARLY: test two opposite corner taps before any load (pm_sweep2_kernel, whose launches fill the GPU and run into the texture-address unit; the speculative kernels of the
-// short launches are bound by a visit's dependent chain, where the test's two extra divisions cost 3 %: profiles/r06_call13/ab_13.log)
+// EARLY: test the first row's two corner taps before any load (pm_sweep2_kernel, whose launches fill the GPU and run into the texture-address unit; the speculative kernels of
+// the short launches are bound by a visit's dependent chain, where a test of two opposite corners, with two divisions of its own, cost 3 %: profiles/r06_call13/ab_13.log)
+// lvu: the launch's size block (pm_make_lvl; pm_sweep2_kernel and the init kernel on the quad buffer), or null: the view's own size from its hot block, the thresholds formed
+// after the tap rows as they always were -- the pointer path, and the speculative kernels, which hold 168 VGPRs and ~100 SGPRs: seven more scalars cost them two more spilled
+// dwords and 0.35 % of the 25-view step (profiles/eval_trim_ab.log).  ddp: PF only, where the prior blend's distance term of this hypothesis waits (pm_visit), or null.
 template <bool GEO, int MODE, bool PF = false, bool EARLY = false>
 __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask& t, const PMKParams& kp,
 		int x, int y, double X0x, double X0y, float normSq0, float sumW, const float2* wts,
 		float depth, float nx, float ny, float nz,
 		float sf0, float sf1, float sf2, float sf3, float prior,
 		const double* hot, const double* geoTab, const PMImgBuf& rs PM_PROF_ARG, const double* rpre = nullptr, const float* sfp = nullptr,
-		const PMGeoReq* greq = nullptr, int gsel = 0, int gn = 1)
+		const PMGeoReq* greq = nullptr, int gsel = 0, int gn = 1, const PMLvl* lvu = nullptr, const float* ddp = nullptr)
 {
-	const int sw = ((const int*)(hot + 12))[0], sh = ((const int*)(hot + 12))[1];
+	// the source image's size block: the launch's (lvu, wave-uniform) or the view's own, from its hot block
+	const PMLvl lv = lvu ? *lvu : pm_lvl_of(((const int*)(hot + 12))[0], ((const int*)(hot + 12))[1]);
+	const int sw = lv.sw, sh = lv.sh;
 	float H[9];
 	pm_homography(hot, t, X0x, X0y, depth, nx, ny, nz, H, rpre);
 	PM_TICK(3);
@@ -810,31 +869,44 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		// |x|, |y| < 1e18 and |z| < 2^40 for every tap of the patch, from the first tap and the step sizes (8 steps along either axis at most)
 		const bool sane = pm_fabsf(X0) + 8.f * (pm_fabsf(H[0]) + pm_fabsf(H[1])) < 5e17f && pm_fabsf(X1) + 8.f * (pm_fabsf(H[3]) + pm_fabsf(H[4])) < 5e17f
 			&& pm_fabsf(X2) + 8.f * (pm_fabsf(H[6]) + pm_fabsf(H[7])) < 5e11f;
-		// Two opposite corner taps first, without loads: the texture-address unit, which bounds the sweep kernels, is paid by the active lane, and a source view
-		// that does not see the pixel at all -- a fifth of the (pixel, view) pairs of the benchmark's grid of cameras -- would otherwise gather all 25 samples for nothing.
-		// Tap (0,0) is the reference's first tap and tap (4,4) its last; their positions are formed by the very additions the rows below perform (four row steps, then four tap
-		// steps), and with z inside [2^-40, 2^40] and sane start values the quotient is the IEEE one (pm_div2_inrange): if either lies outside the image the reference has
-		// returned thRobust at that tap at the latest (DepthMap.cpp:484-485), whatever the other taps do.  A corner whose z is out of range decides nothing here.
+		// The first row's two corner taps, (0,0) and (0,4), are tested before any load (EARLY, pm_row_issue): the texture-address unit, which bounds the sweep kernels
+		// (DESIGN.md 4.1), is paid by the active lane, and a source view that does not see the pixel at all -- a fifth of the (pixel, view) pairs of the benchmark's grid of
+		// cameras -- would otherwise gather all 25 samples for nothing.  Tap (0,0) is the reference's first tap and (0,4) a tap like any other; their positions are the row's own
+		// (needed anyway), and with z inside [2^-40, 2^40] and sane start values the quotient is the IEEE one (pm_div2_inrange): if either lies outside the image the reference
+		// has returned thRobust at that tap at the latest (DepthMap.cpp:484-485), whatever the other taps do.  A corner whose z is out of range decides nothing here, and a patch
+		// that leaves the image further down is caught after the gather by (2) below: thRobust either way.
+		const unsigned qbase = ((const unsigned*)(hot + 13))[0];
+		const pm_gcf4 imgQ = pm_glob4(s.imgQ);
+		const float rX0 = bX0, rX1 = bX1, rX2 = bX2;
+		PMTapRange rg = {0x7fffffff, (int)0x80000000, 0x7fffffff, (int)0x80000000, (int)0x80000000};
+#ifdef PM_PROBE_EARLY_OPPOSITE
+		// measurement builds only (profiles/eval_trim_ab.log): the test this one replaced -- taps (0,0) and (4,4), with two division chains of their own and 24 additions
 		if (EARLY && sane) {
 			bool outside = false;
 			float cx, cy;
-			if (bX2 >= 9.094947e-13f && bX2 <= 1.0995116e12f) { pm_div2_inrange(bX0, bX1, bX2, &cx, &cy); outside = !pm_inside1(cx, cy, sw, sh); }
+			if (bX2 >= 9.094947e-13f && bX2 <= 1.0995116e12f) { pm_div2_inrange(bX0, bX1, bX2, &cx, &cy); outside = !pm_inside1(cx, cy, lv); }
 			float c0 = bX0, c1 = bX1, c2 = bX2;
 #pragma unroll
 			for (int i = 0; i < 4; ++i) { c0 += H[1]; c1 += H[4]; c2 += H[7]; }
 #pragma unroll
 			for (int j = 0; j < 4; ++j) { c0 += H[0]; c1 += H[3]; c2 += H[6]; }
-			if (c2 >= 9.094947e-13f && c2 <= 1.0995116e12f) { pm_div2_inrange(c0, c1, c2, &cx, &cy); outside = outside || !pm_inside1(cx, cy, sw, sh); }
+			if (c2 >= 9.094947e-13f && c2 <= 1.0995116e12f) { pm_div2_inrange(c0, c1, c2, &cx, &cy); outside = outside || !pm_inside1(cx, cy, lv); }
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
 			if (outside) pm_tap_census[PF][3]++;
 #endif
 			if (outside) return kp.thRobust;
 		}
-		const unsigned qbase = ((const unsigned*)(hot + 13))[0];
-		const pm_gcf4 imgQ = pm_glob4(s.imgQ);
-		const float rX0 = bX0, rX1 = bX1, rX2 = bX2;
-		PMTapRange rg = {0x7fffffff, (int)0x80000000, 0x7fffffff, (int)0x80000000, (int)0x80000000};
-		pm_taps_fast<MODE == 2>(rs, qbase, imgQ, sw, sh, H, bX0, bX1, bX2, wts, sum, sumSq, num, rg);
+		constexpr bool EARLY_ = false;
+#elif defined(PM_PROBE_NO_EARLY)
+		constexpr bool EARLY_ = false;   // measurement builds only (profiles/eval_trim_bound.log): no test before the loads anywhere
+#else
+		constexpr bool EARLY_ = EARLY;
+#endif
+		const bool outsideEarly = pm_taps_fast<MODE == 2, EARLY_>(rs, qbase, imgQ, lv, H, bX0, bX1, bX2, wts, sum, sumSq, num, rg, sane);
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
+		if (outsideEarly) pm_tap_census[PF][3]++;
+#endif
+		if (outsideEarly) return kp.thRobust;
 		// (1) exact: 2^-40 <= z <= 2^40 on the whole patch (the extremes of z are among the corners, PMTapRange) and `sane` start values: every quotient of the patch was
 		//     the correctly rounded one, so the sums are pm_tap_row_global's and a tap's position is the one the reference tests.  Otherwise (0 - 11 of 0.3 - 0.9 M evaluations of an
 		//     ordinary 96x72 scene, 33 % with a source that looks the other way: the PM_DEBUG_REDO census, tests/test_emu_tap_fallbacks.py) the whole patch is redone through the guarded path.
@@ -847,9 +919,12 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		// (4) otherwise -- a corner within delta of the border band, or a plane that almost contains the viewing ray: the positions of all 25 taps again (the same float
 		//     operations, no loads), tested one by one as the reference does.
 		const bool exact = sane && rg.zlo >= pm_f2i(9.094947e-13f) && rg.zhi <= pm_f2i(1.0995116e12f);
-		const bool cornersIn = rg.plo >= pm_f2i(1.f) && rg.pxhi <= pm_f2i((float)(sw - 2)) && rg.pyhi <= pm_f2i((float)(sh - 2));
-		const float delta = (float)max(sw, sh) * 7.62939453125e-06f;   // 2^-17
-		const bool allIn = rg.plo >= pm_f2i(1.f + delta) && rg.pxhi <= pm_f2i((float)(sw - 2) - delta) && rg.pyhi <= pm_f2i((float)(sh - 2) - delta)
+		// (a view with its own size forms the thresholds here, from the size, as it always did: formed before the tap rows they would live in five registers across them)
+		int swp = sw, shp = sh;
+		if (!lvu && EARLY) { PM_OPAQUE(swp); PM_OPAQUE(shp); }   // (the bounds of the test before the loads are not kept for this)
+		const PMLvl lp = lvu ? lv : pm_lvl_of(swp, shp);
+		const bool cornersIn = rg.plo >= pm_f2i(1.f) && rg.pxhi <= pm_f2i(lp.xm) && rg.pyhi <= pm_f2i(lp.ym);
+		const bool allIn = rg.plo >= pm_f2i(lp.oneD) && rg.pxhi <= pm_f2i(lp.xmD) && rg.pyhi <= pm_f2i(lp.ymD)   // delta = 2^-17 max(w, h): PMLvl
 			&& (unsigned)rg.zhi - (unsigned)rg.zlo <= 0x00800000u;   // zhi <= 2 zlo on the bit patterns of positive floats (one exponent step)
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
 		pm_tap_census[PF][0]++; if (exact && cornersIn && !allIn) pm_tap_census[PF][1]++; if (!exact) pm_tap_census[PF][2]++;
@@ -865,7 +940,7 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 					for (int j = 0; j < 5; ++j) {
 						float ptx, pty;
 						pm_div2_inrange(X0t, X1t, X2t, &ptx, &pty);
-						oob = oob || !pm_inside1(ptx, pty, sw, sh);
+						oob = oob || !pm_inside1(ptx, pty, lp);
 						X0t += H[0]; X1t += H[3]; X2t += H[6];
 					}
 					cX0 += H[1]; cX1 += H[4]; cX2 += H[7];
@@ -882,6 +957,9 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		}
 	}
 	PM_TICK(4);
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(PM_DEBUG_REDO)
+	if (MODE != 0 && oob) pm_tap_census_outside[PF]++;
+#endif
 	if (oob) return kp.thRobust;
 	const float normSq1 = sumSq - (sum * sum) / sumW;
 	const float nrmSq = normSq0 * normSq1;
@@ -960,12 +1038,15 @@ __device__ __forceinline__ float pm_score_view(const PMSrcView& s, const PMTask&
 		const float2 pf = wts[PM_NT];
 		float pfy = pf.y;
 		PM_OPAQUE(pfy);   // both halves are read at once (the compiler otherwise splits the read and sinks one half under the test of the other)
+#ifndef PM_PROBE_EVAL_TRIM
 		if (pf.x > 0) {
-			const float deltaDepth = pm_minf(pm_fabsf(pf.x - depth) / pf.x, 0.5f);
+			// (pm_sweep2_kernel: the quotient depends on the pixel and the hypothesis, not on the view -- formed once per trip by pm_visit, it waits in the pixel's LDS state)
+			const float deltaDepth = ddp ? *ddp : pm_prior_delta(pf.x, depth);
 			score = (1.f - pfy) * score + pfy * deltaDepth;
 		}
+#endif
 	} else if (prior > 0) {
-		const float deltaDepth = pm_minf(pm_fabsf(prior - depth) / prior, 0.5f);
+		const float deltaDepth = pm_prior_delta(prior, depth);
 		const float sigma = -1.f / (1.f * 0.02f);
 		const float f = pm_expf(normSq0 * sigma);
 		score = (1.f - f) * score + f * deltaDepth;
@@ -1084,12 +1165,13 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_init_kernel(const PMTask* __restr
 	float sc = PM_INF, sc2 = PM_INF;   // the lane's two smallest view scores
 	PM_PROF_DECL;
 	const PMImgBuf rs = MODE == 2 ? pm_make_imgbuf(t) : PMImgBuf();
+	const PMLvl lv = MODE == 2 ? pm_make_lvl(t) : PMLvl();
 #pragma unroll 1
 	for (int u = 0; u < VPL; ++u) {
 		const int vw = v + u * G;
 		if (vw < t.nSrc) {
 			const float s1 = pm_score_view<GEO, MODE>(t.src[vw], t, kp, x, y, X0x, X0y, normSq0, sumW, s_w[g], depth, nx, ny, nz, 1.f, 1.f, 1.f, 1.f, prior, t.src[vw].Hl, (const double*)t.src[vw].Tl,
-				rs PM_PROF_PASS);
+				rs PM_PROF_PASS, nullptr, nullptr, nullptr, 0, 1, MODE == 2 ? &lv : nullptr);
 			if (s1 < sc) { sc2 = sc; sc = s1; } else if (s1 < sc2) sc2 = s1;
 		}
 	}
